@@ -9,8 +9,11 @@ M=4096 particles, N=50, Nc=1 consensus, box constraints on the controls, fp64.  
 4096 particles are sharded N ways (strong scaling), one process per GPU, RCCL all-reduce of the
 consensus Hessian/gradient and of the active-set change counters (interior-point scalars on the fallback path) only.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-HIP-event timed on the solver's own stream) and `cpu_baseline` (oracle timed on a bounded sample).
+Prints ONE JSON line on rank 0: the rate of the W warm-up + K timed SCP iterations (`value`, `ms_per_step`) and the
+workload.  A plain run does nothing else.  With --full the same line also carries `repeats` (the window again from fresh SCP
+starts), `roofline` (dominant kernel, HIP-event timed on the solver's own stream, and the cold sub-problem rate) and
+`cpu_baseline` / `cpu_baseline_structured` (oracle and C baseline timed on a bounded sample).  --dump-outputs DIR writes
+what the timed path returned in its last step (final iterate X, U and the residuals of the K timed steps) as float64 .npy.
 """
 import argparse
 import json
@@ -58,6 +61,27 @@ def pmc_sq_evidence(kernel_prefix):
     return None
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, per_particle, other, M_total):
+    """--dump-outputs: {name: array} as float64 out_dir/<name>.npy.  If everything exceeds DUMP_BYTES_MAX, the `per_particle` arrays
+    (first axis = the M_total particles) keep a fixed, seeded sample of particles, whose indices go to sample_particles.npy."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    per_particle = {k: np.asarray(a, dtype=np.float64) for k, a in per_particle.items()}
+    other = {k: np.asarray(a, dtype=np.float64) for k, a in other.items()}
+    row = sum(a.nbytes // M_total for a in per_particle.values())
+    rest = sum(a.nbytes for a in other.values())
+    if rest + row * M_total > DUMP_BYTES_MAX:
+        keep = (DUMP_BYTES_MAX - rest) // (row + 8)  # (+ 8: the index)
+        idx = np.sort(np.random.default_rng(0).choice(M_total, keep, replace=False))
+        per_particle = {k: a[idx] for k, a in per_particle.items()}
+        other["sample_particles"] = idx.astype(np.float64)
+    for k, a in {**per_particle, **other}.items():
+        np.save(out_dir / f"{k}.npy", np.ascontiguousarray(a))
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -75,7 +99,11 @@ def parse():
     ap.add_argument("--smooth-alpha", type=float, default=float("nan"), help="with --cone: log-barrier smoothing of the boxes (main.jl:246-262); NaN = hard boxes")
     ap.add_argument("--fp32", action="store_true", help="fp32-STORAGE mode (BASELINE config E's dtype; the reference is fp64-only): fx, fu, Q, R and the "
                     "factor records in float32 — half the HBM bytes of the dominant arrays —, arithmetic fp64 (include/pmpc_abi.h PMPC_F32_MATRICES)")
-    ap.add_argument("--repeats", type=int, default=4, help="extra repeats of the timed window from a fresh SCP start (spread; outside `value`)")
+    ap.add_argument("--full", action="store_true", help="beyond the headline rate: repeats of the window, HIP-event roofline of the "
+                    "launch classes, cold sub-problem rate and CPU baselines (--repeats, --profile-all, --no-cpu-baseline act only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: write X.npy, U.npy (final iterate) and "
+                    "scp_residual.npy (residual of each timed step) to DIR, float64, <= 64 MB in all (a seeded sample of particles beyond)")
+    ap.add_argument("--repeats", type=int, default=4, help="--full: extra repeats of the timed window from a fresh SCP start (spread; outside `value`)")
     ap.add_argument("--thrust-min", type=float, default=0.0, help="quadrotor: lower box of the thrust as a fraction of the hover thrust "
                     "(default 0: the thrust cone's apex is feasible; > 0 keeps every cone away from its apex)")
     ap.add_argument("--vmax", type=float, default=0.0, help="quadrotor: state boxes |v| <= VMAX m/s on the three velocity components "
@@ -85,10 +113,10 @@ def parse():
                     "SCP iteration of the first window to stderr")
     ap.add_argument("--python-loop", action="store_true", help="drive the SCP loop from Python (one linearise / solve / residual call per "
                     "iteration) instead of pmpc_scp_loop_device")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baselines out")
     ap.add_argument("--force-generic", action="store_true")
     ap.add_argument("--verbose", nargs="?", const=1, default=0, type=int)
-    ap.add_argument("--profile-all", action="store_true", help="HIP events around every launch class, not only the dominant kernel")
+    ap.add_argument("--profile-all", action="store_true", help="--full: HIP events around every launch class, not only the dominant kernel")
     ap.add_argument("--ignore-status", action="store_true", help="timing experiments with deliberately wrong kernels")
     return ap.parse_args()
 
@@ -343,13 +371,58 @@ def main():
             el = float(t.item())
         return el
 
-    # ---- the contract's timed region: W warm-up + exactly K timed steps (HIP events around the dominant kernel only) ----------
-    elapsed = window(2 if args.profile_all else 1)
+    # ---- the contract's timed region: W warm-up + exactly K timed steps (--full: HIP events around the dominant kernel) ----------
+    elapsed = window((2 if args.profile_all else 1) if args.full else 0)
     prof = solver.profile_read()
     timed = list(hist[args.warmup:])
     if args.trace_steps and rank == 0:
         print("per SCP iteration (ipm iterations, active-set rounds, factorisations):",
               [(h[1]["ipm_iters"], h[1]["active_set_rounds"], h[1]["structured_solves"]) for h in hist], file=sys.stderr)
+    if args.dump_outputs:  # the last timed step's iterate is in (Xa, Ua) (run() swaps it there); every rank's shard, in particle order
+        def gather(t):
+            if world == 1:
+                return t.cpu().numpy()
+            g = torch.empty((world * t.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+            dist.all_gather_into_tensor(g, t.contiguous())
+            return g.cpu().numpy()
+
+        Xd, Ud = gather(Xa), gather(Ua)
+        res_timed = torch.cat([h[0].reshape(-1)[:1] for h in timed]).cpu().numpy()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dict(X=Xd, U=Ud), dict(scp_residual=res_timed), M_total)
+    ipm_its = [h[1]["ipm_iters"] for h in timed]
+    solves = [h[1]["structured_solves"] for h in timed]
+    as_rounds = [h[1]["active_set_rounds"] for h in timed]
+    w0, w1 = args.warmup + 1, args.warmup + args.steps
+    headline = {
+        "metric": "SCP iterations/sec (M particles x N horizon)", "value": args.steps / elapsed, "unit": "SCP iterations/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak" if args.weak else "strong", "vs_baseline": None,
+        "dtype": "f32 storage (fx, fu, Q, R, factor records) / f64 arithmetic" if args.fp32 else "f64", "data": "synthetic",
+        "config": {"workload": (f"{args.model} x{x} u{u} M={M_total} N={N} Nc={Nc} box-u, full SCP iteration "
+                                "(on-device linearise + c_lqp_solve-equivalent + residual), BASELINE config D"
+                                if args.model == "quadrotor" and M_total == 4096 and N == 50 and Nc == 1 and not args.cone and not args.soc and not args.vmax > 0.0 else
+                                f"{args.model} x{x} u{u} M={M_total} N={N} Nc={Nc} box-u" + (" + thrust cone per stage (config E constraints, fp64)" if args.soc else "")
+                                + ((" through the reference's default cone path (c_lcone_solve semantics: eps-anchored epigraph objective"
+                                    + (f", log-barrier smoothing alpha = {args.smooth_alpha:g})" if args.smooth_alpha == args.smooth_alpha else ", hard boxes)")) if args.cone else "")
+                                + (f", thrust >= {args.thrust_min} x hover" if args.thrust_min > 0.0 else "")
+                                + (f", state boxes |v| <= {args.vmax} m/s" if args.vmax > 0.0 else ""))
+                               + f"; timed window = SCP iterations {w0}..{w1} from the cold start X_prev = x0, U_prev = U_ref "
+                                 "(the active-set round count falls as the SCP loop converges, so the rate depends on the window)",
+                   "particles_per_gpu": M_loc, "parallelism": f"particle-shard x{world}",
+                   "scp_loop": "python (one call per linearise / solve / residual)" if args.python_loop else "library (pmpc_scp_loop_device)",
+                   "ipm_iters_per_step": float(np.mean(ipm_its)), "riccati_factorisations_per_step": float(np.mean(solves)),
+                   "active_set_rounds_per_step": float(np.mean(as_rounds)),
+                   "weighted_qps_per_step": float(np.mean([h[1].get("outer_solves", 0) for h in timed])),
+                   "fast_path": bool(timed[-1][1]["fast_path"]), "final_scp_residual": float(timed[-1][0][0].item()),
+                   "ipm_warm_start": os.environ.get("PMPC_WARM_START", "1") != "0"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # ---- repeats of the same window from a fresh SCP start: spread of the measurement; the last one carries HIP events around
     #      every launch class and around the sub-problem (aff_solve) as a whole — outside the reported region ------------------
     rep_s = [elapsed]
@@ -374,12 +447,8 @@ def main():
     aff_only = k2 / (time.perf_counter() - t1)
     prof_cold = solver.profile_read()
     solver.profile(False)
-    ipm_its = [h[1]["ipm_iters"] for h in timed]
-    solves = [h[1]["structured_solves"] for h in timed]
-    as_rounds = [h[1]["active_set_rounds"] for h in timed]
 
     if rank == 0:
-        value = args.steps / elapsed
         ms_f, n_f = prof["bwd_factor"]
         unit_bytes = ELEMS_PER_UNIT * 8 if (x, u) == (12, 4) else (2 * x * x + x * u + u * u + 3 * x + 2 * u + 2 * u + x + u) * 8
         if args.fp32:  # the matrix stacks (2 x^2 + x u + u^2 elements of the unit) are 4-byte entries
@@ -485,30 +554,9 @@ def main():
                                  "wave, operand prefetch and an LDS-only barrier measured: CHANGELOG.md section 5.7), the (Nc u)^2 Cholesky is a chain of Nc u / 16 "
                                  "panels on ONE workgroup (0.12 ms at config D, profiles/r05_cons_solve_micro.txt)"}
         rates = [args.steps / t_ for t_ in rep_s]
-        w0, w1 = args.warmup + 1, args.warmup + args.steps
+        headline["config"]["aff_solve_only_cold_per_s"] = aff_only
         out = {
-            "metric": "SCP iterations/sec (M particles x N horizon)", "value": value, "unit": "SCP iterations/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": "weak" if args.weak else "strong", "vs_baseline": None,
-            "dtype": "f32 storage (fx, fu, Q, R, factor records) / f64 arithmetic" if args.fp32 else "f64", "data": "synthetic",
-            "config": {"workload": (f"{args.model} x{x} u{u} M={M_total} N={N} Nc={Nc} box-u, full SCP iteration "
-                                    "(on-device linearise + c_lqp_solve-equivalent + residual), BASELINE config D"
-                                    if args.model == "quadrotor" and M_total == 4096 and N == 50 and Nc == 1 and not args.cone and not args.soc and not args.vmax > 0.0 else
-                                    f"{args.model} x{x} u{u} M={M_total} N={N} Nc={Nc} box-u" + (" + thrust cone per stage (config E constraints, fp64)" if args.soc else "")
-                                    + ((" through the reference's default cone path (c_lcone_solve semantics: eps-anchored epigraph objective"
-                                        + (f", log-barrier smoothing alpha = {args.smooth_alpha:g})" if args.smooth_alpha == args.smooth_alpha else ", hard boxes)")) if args.cone else "")
-                                    + (f", thrust >= {args.thrust_min} x hover" if args.thrust_min > 0.0 else "")
-                                    + (f", state boxes |v| <= {args.vmax} m/s" if args.vmax > 0.0 else ""))
-                                   + f"; timed window = SCP iterations {w0}..{w1} from the cold start X_prev = x0, U_prev = U_ref "
-                                     "(the active-set round count falls as the SCP loop converges, so the rate depends on the window)",
-                       "particles_per_gpu": M_loc, "parallelism": f"particle-shard x{world}",
-                       "scp_loop": "python (one call per linearise / solve / residual)" if args.python_loop else "library (pmpc_scp_loop_device)",
-                       "ipm_iters_per_step": float(np.mean(ipm_its)), "riccati_factorisations_per_step": float(np.mean(solves)),
-                       "active_set_rounds_per_step": float(np.mean(as_rounds)),
-                       "weighted_qps_per_step": float(np.mean([h[1].get("outer_solves", 0) for h in timed])),
-                       "fast_path": bool(timed[-1][1]["fast_path"]), "final_scp_residual": float(timed[-1][0][0].item()),
-                       "aff_solve_only_cold_per_s": aff_only,
-                       "ipm_warm_start": os.environ.get("PMPC_WARM_START", "1") != "0"},
+            **headline,
             "repeats": {"windows": len(rates), "values": rates, "median": float(np.median(rates)), "min": float(np.min(rates)),
                         "max": float(np.max(rates)),
                         "note": "`value` is the FIRST window (the contract's W + K steps); the others repeat it from a fresh SCP start in the same process"},

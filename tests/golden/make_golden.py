@@ -219,8 +219,31 @@ def more_notebook_tables():
     }
 
 
+PROBLEM_DICT_KW = dict(xdim=4, udim=2, N=9, M=2, Nc=2, reg_x=3.0, X_ref=np.arange(36.0).reshape(9, 4))
+
+
+def problem_dict():
+    """`Problem(**PROBLEM_DICT_KW).to_dict()` of the reference's own builder (pmpc/problem_struct.py) with control boxes
+    -1 / 1: every array entry under its key, every other entry (scalars, None, solver_settings) in the JSON string `meta`,
+    the dynamics callback left out."""
+    import importlib.util
+    import json
+
+    spec = importlib.util.spec_from_file_location("ref_problem_struct", REF / "pmpc" / "problem_struct.py")
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+    p = ref.Problem(**PROBLEM_DICT_KW)
+    p.f_fx_fu_fn = lambda X, U: None
+    p.u_l, p.u_u = -np.ones(2), np.ones(2)
+    d = p.to_dict()
+    arrays = {k: v for k, v in d.items() if isinstance(v, np.ndarray)}
+    meta = {k: v for k, v in d.items() if k not in arrays and k != "f_fx_fu_fn"}
+    return dict(arrays, meta=np.array(json.dumps(dict(entries=meta, keys=sorted(d)))))
+
+
 if __name__ == "__main__":
     orc.build()
+    save("ref_problem_struct_dict.npz", **problem_dict())
     save("ref_notebook_cpu_table.npz", **notebook_table())
     for name, pack in more_notebook_tables().items():
         save(name, **pack)

@@ -385,7 +385,7 @@ def test_library_scp_loop_equals_the_python_driven_loop(solver, model, M, N, Nc)
 
 
 def test_bench_line_keeps_the_driver_contract():
-    """`python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON line with the keys the driver reads, the metric / unit of
+    """`python bench.py --gpus 1 --steps K --warmup W --full` prints ONE JSON line with the keys the driver reads, the metric / unit of
     BASELINE.json, and the `roofline` and `cpu_baseline` objects (small sizes here: the contract, not the numbers)."""
     import json
     import subprocess
@@ -393,7 +393,7 @@ def test_bench_line_keeps_the_driver_contract():
     from pathlib import Path
 
     root = Path(__file__).resolve().parents[1]
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--M", "64", "--N", "12"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--M", "64", "--N", "12", "--full"],
                        cwd=str(root), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -412,6 +412,43 @@ def test_bench_line_keeps_the_driver_contract():
     assert rp["windows"] == 5 and len(rp["values"]) == 5 and rp["min"] <= rp["median"] <= rp["max"] and abs(rp["values"][0] - d["value"]) < 1e-9 * d["value"]
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] == 1 and cb["value"] > 0 and "sample" in cb and "julia" in cb
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` prints the headline line only (no repeats, roofline or CPU baselines), and
+    --dump-outputs DIR writes the last timed step's iterate and the K timed residuals: the same as a Python-driven SCP loop over the
+    same seeded inputs (bench.py --python-loop), and the same again on a second run."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    root = Path(__file__).resolve().parents[1]
+    M, N, steps = 64, 12, 4
+
+    def bench(tag, *extra):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "2", "--M", str(M), "--N", str(N),
+                            "--dump-outputs", str(tmp_path / tag), *extra], cwd=str(root), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0]), {k: np.load(tmp_path / tag / f"{k}.npy") for k in ("X", "U", "scp_residual")}
+
+    d, out = bench("a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    assert not {"repeats", "roofline", "cpu_baseline", "cpu_baseline_structured"} & set(d)
+    assert d["steps"] == steps and d["unit"] == "SCP iterations/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["U.npy", "X.npy", "scp_residual.npy"]
+    assert out["X"].shape == (M, N, 12) and out["U"].shape == (M, N, 4) and out["scp_residual"].shape == (steps,)
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in out.values())
+    assert out["scp_residual"][-1] == d["config"]["final_scp_residual"]
+    _, again = bench("b")
+    _, py = bench("c", "--python-loop")
+    for k in out:
+        np.testing.assert_allclose(again[k], out[k], rtol=1e-8, atol=1e-10, err_msg=k)
+        np.testing.assert_allclose(py[k], out[k], rtol=1e-8, atol=1e-10, err_msg=k)
 
 
 def test_a_context_says_once_when_it_leaves_the_register_resident_path(capfd):

@@ -168,28 +168,26 @@ def test_problem_builder_defaults_and_tiling():
         Problem(N=3, xdim=2)
 
 
-@pytest.mark.skipif(not (ROOT.parent / "reference" / "pmpc" / "problem_struct.py").exists(), reason="needs /root/reference (build container only)")
 def test_problem_builder_matches_reference():
-    import importlib.util
+    """`Problem.to_dict()` against the reference builder's output for the same arguments (stored by
+    tests/golden/make_golden.py: arrays under their keys, every other entry in the JSON string `meta`)."""
+    import json
 
     from pmpc_amd.problem_struct import Problem
 
-    spec = importlib.util.spec_from_file_location("ref_problem_struct", ROOT.parent / "reference" / "pmpc" / "problem_struct.py")
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    g = np.load(GOLD / "ref_problem_struct_dict.npz")
+    meta = json.loads(str(g["meta"]))
     kw = dict(xdim=4, udim=2, N=9, M=2, Nc=2, reg_x=3.0, X_ref=np.arange(36.0).reshape(9, 4))
-    a, b = Problem(**kw), ref.Problem(**kw)
-    fn = lambda X, U: None
-    for p in (a, b):
-        p.f_fx_fu_fn = fn
-        p.u_l, p.u_u = -np.ones(2), np.ones(2)
-    da, db = a.to_dict(), b.to_dict()
-    assert set(da) == set(db)
-    for k in db:
-        if isinstance(db[k], np.ndarray):
-            np.testing.assert_array_equal(da[k], db[k], err_msg=k)
+    a = Problem(**kw)
+    a.f_fx_fu_fn = lambda X, U: None
+    a.u_l, a.u_u = -np.ones(2), np.ones(2)
+    da = a.to_dict()
+    assert set(da) == set(meta["keys"])
+    for k in meta["keys"]:
+        if k in g.files:
+            np.testing.assert_array_equal(da[k], g[k], err_msg=k)
         elif k != "f_fx_fu_fn":
-            assert da[k] == db[k], k
+            assert da[k] == meta["entries"][k], k
 
 
 @pytest.mark.parametrize("case_idx", [0, 3, 5, 7, 8, 9, 10, 13, 14, 28])

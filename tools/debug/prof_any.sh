@@ -2,9 +2,10 @@
 tag=$1; shift
 out=gpurun_out/prof_$tag
 mkdir -p $out
+root=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /root/repo/$out -- python3 /root/repo/bench.py --steps 10 --warmup 2 --repeats 0 --no-cpu-baseline "$@" > /root/repo/$out/out.log 2>&1 || exit 1
-cd /root/repo
+rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out -- python3 $root/bench.py --full --steps 10 --warmup 2 --repeats 0 --no-cpu-baseline "$@" > $root/$out/out.log 2>&1 || exit 1
+cd $root
 python - <<PY
 import csv,glob
 f=glob.glob("$out/**/*kernel_stats.csv",recursive=True)[0]

@@ -26,7 +26,7 @@ FWD = ["entry -> 3 MFMAs issued (waits for this stage's loads)", "control word g
 def child(M):
     os.environ["PMPC_HIP_LIB"] = str(ROOT / "libs_tmp" / "libpmpc_hip_tl.so")
     sys.path.insert(0, str(ROOT))
-    sys.argv = ["bench.py", "--steps", "8", "--warmup", "3", "--repeats", "0", "--no-cpu-baseline", "--M", str(M)]
+    sys.argv = ["bench.py", "--full", "--steps", "8", "--warmup", "3", "--repeats", "0", "--no-cpu-baseline", "--M", str(M)]
     import io
     import contextlib
 
