@@ -1,6 +1,8 @@
 // solver_internal.h — what the translation units of the host side share: the context (pmpc_ctx), its workspace, the option table's
 // indices, and the helpers every solve path uses (collectives, device-published scalars, the structured Newton solve).
-//   solver.hip       contexts / options / communicators / profiling, the QP path (solve_impl_body, slew increment form), the SCP loop
+//   solver.hip       contexts / options / communicators / profiling, the structured Newton solve, the fp32-storage protocol and the
+//                    slew increment form around the QP path, the SCP loop
+//   solver_qp.hip    the QP path itself (solve_impl_body): one QpSolve object per solve, one method per phase
 //   solver_cone.hip  the cone objective (c_lcone_solve semantics): hard boxes, smoothed boxes, free particles, particle costs
 //   solver_host.hip  the host-pointer drop-in entry points (c_lqp_solve, c_lcone_solve and their extensions)
 #pragma once
@@ -213,9 +215,14 @@ void fill_nan_outputs(pmpc_ctx *c, const pmpc_problem *p);
 
 }  // namespace pmpc_impl
 
+constexpr int PMPC_NEEDS_F64 = -7;  // solve_impl_body on an fp32-storage problem: this solve needs a path that runs the fp64 kernels
+
 // defined inside the extern "C" blocks of the translation units (C linkage names, C++ signatures): shared between them
 extern "C" {
 pmpc_problem widened_f32_problem(pmpc_ctx *c, const pmpc_problem *p, bool jacobians = true);  // solver.hip: fp32-stored matrix stacks widened for the fp64 paths
 void build_slew_increment_problem(pmpc_ctx *c, const pmpc_problem *p, pmpc_problem &q, SlewAug &g);  // solver.hip: slew penalties restated in control increments
 int lcone_body(pmpc_ctx *c, const pmpc_problem *p, double smooth_alpha, pmpc_info *info, int verbose);  // solver_cone.hip
+int solve_impl_body(pmpc_ctx *c, const pmpc_problem *p, pmpc_info *info, int verbose, bool soc);  // solver_qp.hip: one sub-problem on the QP path
+bool slew_increment_form_applies(const pmpc_ctx *c, const pmpc_problem *p, bool soc);  // solver.hip
+int solve_slew_increment_form(pmpc_ctx *c, const pmpc_problem *p, pmpc_info *info, int verbose);  // solver.hip: calls solve_impl_body on the restated problem
 }
