@@ -281,6 +281,18 @@ int pmpc_linearize_device(pmpc_ctx *ctx, int model, size_t N, size_t M, const do
 int pmpc_linearize_device_f32(pmpc_ctx *ctx, int model, size_t N, size_t M, const double *x0, const double *X_prev,
                               const double *U_prev, const double *params, double *f, float *fx, float *fu);
 
+/* Compact Jacobian records of a built-in model — what pmpc_scp_loop_device writes into its fx scratch arrays instead of the dense
+ * stacks when the coming solve is a warm attempt of the active-set rounds (PMPC_LIN_COMPACT=0 switches that off).  For tests and
+ * tools: the linearisation into jc (pmpc_jac_compact_doubles(model, N, M) doubles; f dense), the expansion of jc into the dense
+ * fx / fu (orient 0 / 1: through the part of the records the factor / the forward sweep reads; jc must not overlap fx, fu), and the
+ * entries the records treat as live (host only, no device needed: fx_mask xdim*xdim, fu_mask xdim*udim bytes, column-major blocks as
+ * in fx / fu; returns 100 xdim + udim, -1 for an unknown model). */
+int pmpc_linearize_compact_device(pmpc_ctx *ctx, int model, size_t N, size_t M, const double *x0, const double *X_prev,
+                                  const double *U_prev, const double *params, double *f, double *jc);
+int pmpc_expand_jac_device(pmpc_ctx *ctx, int model, size_t N, size_t M, const double *jc, double *fx, double *fu, int orient);
+long long pmpc_jac_compact_doubles(int model, size_t N, size_t M);
+int pmpc_jac_live_mask(int model, unsigned char *fx_mask, unsigned char *fu_mask);
+
 /* SCP residual of one iteration (pmpc/scp_mpc.py:397-403): *out (device, one double) = max over particles and stages of
  * ||X - X_prev||_2 and ||U - U_prev||_2 (inf if a trajectory holds a NaN); asynchronous on pmpc_stream(). */
 int pmpc_scp_residual_device(pmpc_ctx *ctx, size_t xdim, size_t udim, size_t N, size_t M, const double *X, const double *X_prev,
@@ -293,7 +305,8 @@ int pmpc_scp_residual_device(pmpc_ctx *ctx, size_t xdim, size_t udim, size_t N, 
  *              pairs (X_prev, U_prev) and (X_out, U_out) swap roles every iteration), p->f / fx / fu are scratch the
  *              linearisation writes (device, caller-allocated), f2 / fx2 / fu2 a second set of the same sizes: the next
  *              linearisation is enqueued behind the sub-problem's rounds BEFORE the host knows they sufficed (if they did
- *              not, it is redone), and must not touch what a continued solve still reads
+ *              not, it is redone), and must not touch what a continued solve still reads.  What the scratch sets hold on return is
+ *              unspecified: for warm solves the loop keeps compact Jacobian records in fx and leaves fu unwritten (see above)
  *   first_cold non-zero: X_prev / U_prev of the first iteration are not the previous solve's outputs (no warm-start promise)
  *   res        device, `steps` doubles: the residual of each iteration (max over ranks when sharded)
  *   infos      host, `steps` entries (may be NULL)

@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "pmpc_profile_enable", "pmpc_profile_read", "pmpc_version", "pmpc_lcone_solve_device", "pmpc_particle_costs_device", "pmpc_lsoc_solve_device", "pmpc_comm_init_mock",
     "pmpc_scp_residual_device", "pmpc_profile_read_partial", "pmpc_profile_read_all", "pmpc_scp_loop_device", "pmpc_linearize_device_f32",
     "pmpc_set_option", "pmpc_get_option", "pmpc_abi_struct_sizes", "pmpc_lcone_solve_host_ex", "pmpc_restart_stats",
+    "pmpc_linearize_compact_device", "pmpc_expand_jac_device", "pmpc_jac_compact_doubles", "pmpc_jac_live_mask",
 ]
 
 
@@ -103,6 +104,15 @@ def load():
     lib.pmpc_linearize_device.restype = ctypes.c_int
     lib.pmpc_linearize_device_f32.argtypes = [vp, ctypes.c_int, sz, sz] + [vp] * 7
     lib.pmpc_linearize_device_f32.restype = ctypes.c_int
+    if hasattr(lib, "pmpc_jac_live_mask"):  # (an A/B library of an older source, PMPC_HIP_LIB, may lack the compact-record entry points)
+        lib.pmpc_linearize_compact_device.argtypes = [vp, ctypes.c_int, sz, sz] + [vp] * 6
+        lib.pmpc_linearize_compact_device.restype = ctypes.c_int
+        lib.pmpc_expand_jac_device.argtypes = [vp, ctypes.c_int, sz, sz, vp, vp, vp, ctypes.c_int]
+        lib.pmpc_expand_jac_device.restype = ctypes.c_int
+        lib.pmpc_jac_compact_doubles.argtypes = [ctypes.c_int, sz, sz]
+        lib.pmpc_jac_compact_doubles.restype = ctypes.c_longlong
+        lib.pmpc_jac_live_mask.argtypes = [ctypes.c_int, vp, vp]
+        lib.pmpc_jac_live_mask.restype = ctypes.c_int
     lib.pmpc_scp_residual_device.argtypes = [vp, sz, sz, sz, sz] + [vp] * 5
     lib.pmpc_scp_residual_device.restype = ctypes.c_int
     lib.pmpc_profile_enable.argtypes = [vp, ctypes.c_int]
@@ -132,6 +142,17 @@ def load():
                           f"{sp.value}/{si.value} bytes, binding {ctypes.sizeof(PmpcProblem)}/{ctypes.sizeof(PmpcInfo)}: rebuild the library")
     _lib = lib
     return lib
+
+
+def jac_live_mask(model: int, x: int, u: int):
+    """(fx_mask (x, x), fu_mask (x, u)) as [row, column] boolean arrays: the Jacobian entries of a built-in model that its compact
+    records store per (particle, stage); every other entry is taken as a constant of the particle.  Host only."""
+    lib = load()
+    mx, mu = np.zeros(x * x, dtype=np.uint8), np.zeros(x * u, dtype=np.uint8)
+    got = lib.pmpc_jac_live_mask(int(model), mx.ctypes.data, mu.ctypes.data)
+    if got != 100 * x + u:
+        raise ValueError(f"model {model}: compact records are for dims {got // 100} x {got % 100}, not {x} x {u}")
+    return mx.reshape(x, x).T.astype(bool), mu.reshape(u, x).T.astype(bool)  # (column-major blocks)
 
 
 def dptr(a: np.ndarray):

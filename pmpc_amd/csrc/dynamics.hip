@@ -12,6 +12,7 @@
 // in all three stacks, so every store instruction writes 64 consecutive doubles (8-byte stores scattered inside each
 // thread's own 1152-byte block reached 1.9 TB/s; the staged version is write-bandwidth bound).
 #include "pmpc_dev.h"
+#include "jac_compact.h"
 #include <cstring>
 #include <cstdlib>
 
@@ -19,11 +20,13 @@ namespace {
 
 struct Unicycle {
   static constexpr int X = 4, U = 2, UNITS = 64;
+  typedef jacc::UnicycleSpec Spec;  // which entries of fx / fu the code below makes depend on the state or the control (jac_compact.h)
   static __device__ __forceinline__ void eval(long long idx, int N, const double *x0, const double *X_prev, const double *U_prev,
                                               const double *params, double *fo, double *A, double *B);
 };
 struct Quadrotor {
   static constexpr int X = 12, U = 4, UNITS = 32;  // 32 records of 204 doubles = 52 KB of LDS
+  typedef jacc::QuadrotorSpec Spec;
   static __device__ __forceinline__ void eval(long long idx, int N, const double *x0, const double *X_prev, const double *U_prev,
                                               const double *params, double *fo, double *A, double *B);
 };
@@ -192,6 +195,73 @@ void launch_model(int N, int M, const double *x0, const double *X_prev, const do
     hipLaunchKernelGGL((k_linearize<Model, double>), dim3(grid + (unsigned)res.nblk), dim3(PMPC_LIN_THREADS), Model::UNITS * LD * sizeof(double), s, N, tot, x0,
                        X_prev, U_prev, params, f, fx, fu, res);
 }
+// Compact variant (jac_compact.h): f dense, and per unit a record of the triples with a live entry instead of the dense fx / fu —
+// 81 doubles per quadrotor unit instead of 204 (the dense kernel is bound by its write stream).  The model runs on a zeroed
+// per-thread copy of the dense unit that never leaves the registers (every index below is a compile-time constant), the record is
+// staged through LDS so that the stores stay coalesced; nothing is cleared.  The thread of stage 0 also writes its particle's
+// constant pool.  jc: [tot records | M pools].
+constexpr int LIN_CUNITS = 64;
+template <class Model>
+__global__ void __launch_bounds__(PMPC_LIN_THREADS) k_linearize_compact(int N, long long tot, const double *x0, const double *X_prev, const double *U_prev,
+                                                                         const double *params, double *f, double *jc, ResArgs res) {
+  typedef jacc::Compact<typename Model::Spec> C;
+  constexpr int X = Model::X, U = Model::U, UNITS = LIN_CUNITS, REC = C::REC, POOL = C::POOL;
+  {
+    const int glin = (int)gridDim.x - res.nblk;
+    if ((int)blockIdx.x >= glin) {
+      residual_block((int)blockIdx.x - glin, res.nblk, res.X, res.Xp, res.rows, res.x, res.U, res.Up, res.rows, res.u, res.out_bits);
+      return;
+    }
+  }
+  constexpr int LD = (X + REC) | 1;  // odd record stride: conflict-free LDS stores
+  extern __shared__ double rec[];
+  const int t = threadIdx.x;
+  const long long first = (long long)blockIdx.x * UNITS;
+  if (t < UNITS && first + t < tot) {
+    double J[X * X + X * U] = {};
+    double *mine = rec + t * LD;
+    Model::eval(first + t, N, x0, X_prev, U_prev, params, mine, J, J + X * X);
+#pragma unroll
+    for (int k = 0; k < REC; k++) mine[X + k] = J[C::tab.rec_src[k]];
+    if ((first + t) % N == 0) {
+      double *pool = jc + tot * REC + ((first + t) / N) * POOL;
+#pragma unroll
+      for (int k = 0; k < POOL; k++) pool[k] = C::tab.pool_src[k] < 0 ? 0.0 : J[C::tab.pool_src[k] < 0 ? 0 : C::tab.pool_src[k]];
+    }
+  }
+  __syncthreads();
+  const int n = (int)((tot - first) < UNITS ? (tot - first) : UNITS);
+  for (int e = t; e < n * X; e += PMPC_LIN_THREADS) f[first * X + e] = rec[(e / X) * LD + e % X];
+  for (int e = t; e < n * REC; e += PMPC_LIN_THREADS) jc[first * REC + e] = rec[(e / REC) * LD + X + e % REC];
+}
+
+// compact records -> the dense stacks (a solve that leaves the warm active-set path; tests).  orient: read every entry through the
+// column-oriented (0) or the row-oriented (1) part of the record — the same values by construction.  jc must not overlap fx / fu.
+template <class Model>
+__global__ void __launch_bounds__(256) k_expand_jac(int N, long long tot, const double *jc, double *fx, double *fu, int orient) {
+  typedef jacc::Compact<typename Model::Spec> C;
+  constexpr int X = Model::X, U = Model::U, XX = X * X, XU = X * U, D = XX + XU;
+  const long long n = tot * D;
+  for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < n; k += (long long)gridDim.x * 256) {
+    const long long unit = k / D;
+    const int e = (int)(k % D);
+    const int m = C::tab.expand[orient ? 1 : 0][e];
+    const double v = m >= 0 ? jc[unit * C::REC + m] : jc[tot * C::REC + (unit / N) * C::POOL + (-1 - m)];
+    if (e < XX) fx[unit * XX + e] = v;
+    else fu[unit * XU + (e - XX)] = v;
+  }
+}
+
+template <class Model>
+void launch_model_compact(int N, int M, const double *x0, const double *X_prev, const double *U_prev, const double *params, double *f,
+                          double *jc, const ResArgs &res, hipStream_t s) {
+  typedef jacc::Compact<typename Model::Spec> C;
+  const long long tot = (long long)M * N;
+  constexpr int LD = (Model::X + C::REC) | 1;
+  const unsigned grid = (unsigned)((tot + LIN_CUNITS - 1) / LIN_CUNITS);
+  hipLaunchKernelGGL((k_linearize_compact<Model>), dim3(grid + (unsigned)res.nblk), dim3(PMPC_LIN_THREADS), LIN_CUNITS * LD * sizeof(double), s, N, tot,
+                     x0, X_prev, U_prev, params, f, jc, res);
+}
 __global__ void __launch_bounds__(256) k_widen_f32(const float *src, double *dst, long long n) {
   for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < n; k += (long long)gridDim.x * 256) dst[k] = (double)src[k];
 }
@@ -212,6 +282,45 @@ void launch_linearize(int model, int N, int M, const double *x0, const double *X
   memset(&none, 0, sizeof(none));
   if (model == 0) launch_model<Unicycle>(N, M, x0, X_prev, U_prev, params, f, fx, fu, none, s, jac32);
   else launch_model<Quadrotor>(N, M, x0, X_prev, U_prev, params, f, fx, fu, none, s, jac32);
+}
+// compact variant: jc (the caller's fx scratch array) receives [M N records | M pools]; res_out null: no residual blocks
+void launch_linearize_compact(int model, int N, int M, const double *x0, const double *X_prev, const double *U_prev, const double *params,
+                              double *f, double *jc, const double *Xr, const double *Xrp, const double *Ur, const double *Urp, int x, int u,
+                              double *res_out, hipStream_t s) {
+  ResArgs r;
+  memset(&r, 0, sizeof(r));
+  if (res_out) {
+    r.X = Xr; r.Xp = Xrp; r.U = Ur; r.Up = Urp; r.rows = (long long)M * N; r.x = x; r.u = u;
+    r.nblk = (int)residual_blocks(r.rows);
+    r.out_bits = (unsigned long long *)res_out;
+  }
+  if (model == 0) launch_model_compact<Unicycle>(N, M, x0, X_prev, U_prev, params, f, jc, r, s);
+  else launch_model_compact<Quadrotor>(N, M, x0, X_prev, U_prev, params, f, jc, r, s);
+}
+bool jac_compact_dims(int model, int x, int u) { return model == 0 ? (x == Unicycle::X && u == Unicycle::U) : (model == 1 && x == Quadrotor::X && u == Quadrotor::U); }
+long long jac_compact_doubles(int model, int N, int M) {
+  const long long tot = (long long)M * N;
+  return model == 0 ? tot * jacc::Compact<jacc::UnicycleSpec>::REC + (long long)M * jacc::Compact<jacc::UnicycleSpec>::POOL
+                    : tot * jacc::Compact<jacc::QuadrotorSpec>::REC + (long long)M * jacc::Compact<jacc::QuadrotorSpec>::POOL;
+}
+void launch_expand_jac(int model, int N, int M, const double *jc, double *fx, double *fu, int orient, hipStream_t s) {
+  const long long tot = (long long)M * N;
+  long long b = (tot * (model == 0 ? 24 : 192) + 255) / 256;
+  if (b > 8192) b = 8192;
+  if (model == 0) hipLaunchKernelGGL((k_expand_jac<Unicycle>), dim3((unsigned)b), dim3(256), 0, s, N, tot, jc, fx, fu, orient);
+  else hipLaunchKernelGGL((k_expand_jac<Quadrotor>), dim3((unsigned)b), dim3(256), 0, s, N, tot, jc, fx, fu, orient);
+}
+// which entries of fx (x*x, column-major) / fu (x*u, column-major) the compact records treat as live (1) — host-side, for the tests
+int jac_live_mask(int model, unsigned char *fx_mask, unsigned char *fu_mask) {
+  auto fill = [&](auto spec) {
+    typedef jacc::Compact<decltype(spec)> C;
+    for (int c = 0; c < C::X + C::U; c++)
+      for (int r = 0; r < C::X; r++) (c < C::X ? fx_mask[r + C::X * c] : fu_mask[r + C::X * (c - C::X)]) = C::cls(r, c) == -1;
+    return C::X * 100 + C::U;
+  };
+  if (model == 0) return fill(jacc::UnicycleSpec{});
+  if (model == 1) return fill(jacc::QuadrotorSpec{});
+  return -1;
 }
 void launch_widen_f32(const float *src, double *dst, long long n, hipStream_t s) {
   long long b = (n + 255) / 256;

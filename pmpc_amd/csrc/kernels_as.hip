@@ -22,6 +22,7 @@
 
 #include "fast_common.h"
 #include "as_ctl_dev.h"
+#include "jac_compact.h"
 
 // Diagnostic build only (-DPMPC_STAGE_TIMELINE, tools/micro/stage_timeline.py; never in the shipped library): s_memtime stamps at the
 // phase boundaries of every stage of ONE wave (the block in the middle of the grid) of the two sweeps, written to a buffer of their
@@ -136,7 +137,20 @@ __global__ void __launch_bounds__(64, MODE == 2 ? 2 : (MODE == 1 ? PMPC_AS_DEEP_
   const bool fF = L.cxv || L.cu;
   const MT *pF = L.cxv ? (const MT *)a.fx + (pbase + jtop) * (XD * XD) + XD * L.oc + L.row0
                        : (L.cu ? (const MT *)a.fu + (pbase + jtop) * (XD * UD) + XD * L.cb + L.row0 : (const MT *)Z);
-  const int sF = fF ? -(int)MB * (L.cxv ? XD * XD : XD * UD) : 0;
+  int sF = fF ? -(int)MB * (L.cxv ? XD * XD : XD * UD) : 0;
+  // compact records (jac_compact.h): the same triple from the unit's record (stage stride = record size) or, when it holds no
+  // live entry, from the particle's constant pool (stage stride 0) — the lane map is a compile-time table, the stages see no change
+  typedef typename jacc::SpecFor<XD, UD>::type JSpec;
+  if constexpr (!std::is_void<JSpec>::value && std::is_same<MT, double>::value) {
+    if (a.jac_compact) {
+      typedef jacc::Compact<JSpec> JC;
+      const int m = JC::tab.bwd[lane];
+      if (m != jacc::NONE) {
+        pF = m >= 0 ? (const MT *)a.fx + (pbase + jtop) * JC::REC + m : (const MT *)a.fx + (size_t)a.M * N * JC::REC + (size_t)i * JC::POOL + (-1 - m);
+        sF = m >= 0 ? -(int)MB * JC::REC : 0;
+      }
+    }
+  }
   // everything else: UNIFORM stage base (scalar registers, advanced by the scalar unit) + a per-lane constant byte offset.
   // Lanes without an entry read entry 0 of the stage block (finite data) and are masked by a zero factor or a select.
   const unsigned lQ = (unsigned)((L.cxv ? XD * L.oc + L.row0 : 0) * MB);
@@ -582,6 +596,18 @@ __global__ void __launch_bounds__(64, 4) k_fwd_as(LQArgs a) {
   } else if (L.cu) {
     pA = (const char *)((const MT *)a.K + pbase * 64 + 16 * L.cb + g);
     sAr = 4 * MB; sAj = 64 * MB;
+  }
+  typedef typename jacc::SpecFor<XD, UD>::type JSpec;
+  if constexpr (!std::is_void<JSpec>::value && std::is_same<MT, double>::value) {
+    // compact records (jac_compact.h): the row triple is KS consecutive doubles of the unit's record, or of the particle's constant pool
+    if (a.jac_compact && L.cxv) {
+      typedef jacc::Compact<JSpec> JC;
+      const double *rec = a.fx + pbase * JC::REC, *pool = a.fx + (size_t)a.M * N * JC::REC + (size_t)i * JC::POOL;
+      const int mA = JC::tab.fwdA[lane], mB = JC::tab.fwdB[lane];
+      pA = (const char *)(mA >= 0 ? rec + mA : pool + (-1 - mA));
+      sAr = MB; sAj = mA >= 0 ? JC::REC * MB : 0;
+      if (gu) { pB = (const char *)(mB >= 0 ? rec + mB : pool + (-1 - mB)); sBj = mB >= 0 ? JC::REC * MB : 0; }
+    }
   }
   bool vA[KS];  // (padding: state column KS g + r beyond xdim -> zero; the record holds zeros there already)
 #pragma unroll

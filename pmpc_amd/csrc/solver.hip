@@ -525,6 +525,36 @@ int pmpc_linearize_device(pmpc_ctx *c, int model, size_t N, size_t M, const doub
   return 0;
 }
 
+// compact Jacobian records of a built-in model (jac_compact.h), as the SCP loop writes and reads them: the linearisation into jc
+// (pmpc_jac_compact_doubles doubles), and the expansion of jc into the dense fx / fu through the column- (orient 0) or row-oriented
+// (1) part of the records.  pmpc_jac_live_mask: the entries the records treat as live (host only; returns 100 xdim + udim).
+int pmpc_linearize_compact_device(pmpc_ctx *c, int model, size_t N, size_t M, const double *x0, const double *X_prev, const double *U_prev,
+                                  const double *params, double *f, double *jc) {
+  try {
+    HIP_CHECK(hipSetDevice(c->device));
+    if (model < 0 || model > 1) return 2;
+    ProfScope ps(c, 6);
+    launch_linearize_compact(model, (int)N, (int)M, x0, X_prev, U_prev, params, f, jc, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream);
+    HIP_CHECK(hipGetLastError());
+  } catch (const PmpcHipError &) {
+    return 2;
+  }
+  return 0;
+}
+int pmpc_expand_jac_device(pmpc_ctx *c, int model, size_t N, size_t M, const double *jc, double *fx, double *fu, int orient) {
+  try {
+    HIP_CHECK(hipSetDevice(c->device));
+    if (model < 0 || model > 1) return 2;
+    launch_expand_jac(model, (int)N, (int)M, jc, fx, fu, orient, c->stream);
+    HIP_CHECK(hipGetLastError());
+  } catch (const PmpcHipError &) {
+    return 2;
+  }
+  return 0;
+}
+long long pmpc_jac_compact_doubles(int model, size_t N, size_t M) { return (model < 0 || model > 1) ? -1 : jac_compact_doubles(model, (int)N, (int)M); }
+int pmpc_jac_live_mask(int model, unsigned char *fx_mask, unsigned char *fu_mask) { return jac_live_mask(model, fx_mask, fu_mask); }
+
 // -------------------------------------------------------------------------------------------------
 // fp32-storage problem -> the same problem with fx, fu, Q, R widened (exactly) into workspace copies, flag cleared
 pmpc_problem widened_f32_problem(pmpc_ctx *c, const pmpc_problem *p, bool jacobians) {
@@ -685,6 +715,17 @@ int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmp
   const bool soc = p0->soc_u_interior != nullptr || p0->cone_count > 0;
   const bool cone_obj = (p0->flags & PMPC_CONE_OBJECTIVE) != 0;  // the sub-problem is the reference's default path (c_lcone_solve)
   const int jac32 = (p0->flags & PMPC_F32_MATRICES) ? 1 : 0;  // (f / fx / fu scratch sets: fx, fu FLOAT arrays then)
+  // Compact Jacobian records (jac_compact.h) instead of the dense fx / fu — a third of the bytes of the one kernel of the step that is
+  // bound by its write stream — whenever the coming solve is expected to be a warm attempt of the active-set rounds without a rollout
+  // (QpSolve::as_start, use_defect), whose sweeps read the records as they are; a solve that takes another turn expands them first
+  // (QpSolve::densify).  PMPC_LIN_COMPACT=0 switches them off (A/B).
+  static const bool lin_compact_env = !(getenv("PMPC_LIN_COMPACT") && atoi(getenv("PMPC_LIN_COMPACT")) == 0);
+  const bool compact_ok = lin_compact_env && !cone_obj && !jac32 && !c->multi() && p0->Nc >= 0 && p0->Nc <= 1 &&
+                          jac_compact_dims(model, (int)p0->xdim, (int)p0->udim) && (p0->flags & PMPC_SYMMETRIC_COST) &&
+                          !(p0->flags & (PMPC_HAS_SLEW | PMPC_HAS_SLEW0 | PMPC_FORCE_GENERIC | PMPC_COLD_START)) &&
+                          ((p0->flags & PMPC_HAS_UBOUNDS) || soc) && !(p0->barrier_mu > 0.0) && c->opt[OPT_AS_DEFECT] != 0.0 &&
+                          c->opt[OPT_AS_WARM] != 0.0 && c->opt[OPT_POLISH_MU] > 0.0;
+  bool compact_set[2] = {false, false};  // what the linearisation buffer sets hold
   int done = 0, cur = 0;
   bool lin_ready = false;  // the linearisation of iteration `done` is already enqueued (valid speculation of the previous one)
   try {
@@ -694,9 +735,15 @@ int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmp
       double *Xp = (done & 1) ? XB : XA, *Up = (done & 1) ? UB : UA, *Xo = (done & 1) ? XA : XB, *Uo = (done & 1) ? UA : UB;
       if (!lin_ready) {
         ProfScope ps(c, 6);
-        launch_linearize(model, (int)p.N, (int)p.M, p.x0, Xp, Up, params, F[cur][0], F[cur][1], F[cur][2], c->stream, jac32);
+        compact_set[cur] = compact_ok && (done > 0 || !first_cold);
+        if (compact_set[cur])
+          launch_linearize_compact(model, (int)p.N, (int)p.M, p.x0, Xp, Up, params, F[cur][0], F[cur][1], nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream);
+        else
+          launch_linearize(model, (int)p.N, (int)p.M, p.x0, Xp, Up, params, F[cur][0], F[cur][1], F[cur][2], c->stream, jac32);
       }
       p.f = F[cur][0]; p.fx = F[cur][1]; p.fu = F[cur][2];
+      c->jac_compact_fx = compact_set[cur] ? F[cur][1] : nullptr;
+      c->jac_compact_model = model;
       p.X_prev = Xp; p.U_prev = Up; p.X_out = Xo; p.U_out = Uo;
       p.flags = p0->flags | PMPC_STATIC_CONS_BOUNDS;
       if (done > 0 || !first_cold) p.flags |= PMPC_PREV_IS_LAST_SOLUTION;
@@ -706,8 +753,13 @@ int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmp
         const bool next = with_next_lin && done + 1 < steps;
         if (next && !res_dirty && !c->multi()) {  // both in ONE launch (independent work)
           ProfScope ps(c, 6);
-          launch_linearize_with_residual(model, (int)p.N, (int)p.M, p.x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], Xo, Xp, Uo,
-                                         Up, (int)p.xdim, (int)p.udim, res + done, c->stream, jac32);
+          compact_set[cur ^ 1] = compact_ok;
+          if (compact_ok)
+            launch_linearize_compact(model, (int)p.N, (int)p.M, p.x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], Xo, Xp, Uo, Up, (int)p.xdim,
+                                     (int)p.udim, res + done, c->stream);
+          else
+            launch_linearize_with_residual(model, (int)p.N, (int)p.M, p.x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], Xo, Xp, Uo,
+                                           Up, (int)p.xdim, (int)p.udim, res + done, c->stream, jac32);
           res_dirty = true;
           return;
         }
@@ -719,7 +771,11 @@ int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmp
         if (c->multi()) allreduce(c, res + done, 1, ncclFloat64, ncclMax);
         if (next) {
           ProfScope ps(c, 6);
-          launch_linearize(model, (int)p.N, (int)p.M, p.x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], c->stream, jac32);
+          compact_set[cur ^ 1] = compact_ok;
+          if (compact_ok)
+            launch_linearize_compact(model, (int)p.N, (int)p.M, p.x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream);
+          else
+            launch_linearize(model, (int)p.N, (int)p.M, p.x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], c->stream, jac32);
         }
       };
       c->spec_fired = c->spec_ok = false;
@@ -728,6 +784,7 @@ int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmp
       const int st = cone_obj ? lcone_body(c, &p, p.barrier_mu > 0.0 ? 1.0 / p.barrier_mu : std::numeric_limits<double>::quiet_NaN(), &inf, 0)
                               : solve_impl(c, &p, &inf, 0, soc);
       c->post_batch = nullptr;
+      c->jac_compact_fx = nullptr;
       if (infos) infos[done] = inf;
       if (st != 0) break;
       if (c->spec_fired && c->spec_ok) {
@@ -741,6 +798,7 @@ int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmp
     HIP_CHECK(hipGetLastError());
   } catch (const PmpcHipError &) {
     c->post_batch = nullptr;
+    c->jac_compact_fx = nullptr;
     if (infos && done < steps) { memset(&infos[done], 0, sizeof(pmpc_info)); infos[done].status = 2; }
     fail_after_error(c, nullptr, nullptr);
     // both trajectory pairs hold unfinished iterates now: NaN, as every single-solve entry does with its outputs (res[done..] is

@@ -67,6 +67,7 @@ struct Workspace {
   DevBuf cone_A, cone_c, cone_z, cone_rec, cone_uraw, as_open;  // stage cones inside the active-set rounds (kernels_cone.hip)
   DevBuf xb_qmax;  // per particle: largest diagonal cost entry (penalty scale of the state rows), found once per attempt
   DevBuf xb_z, xb_st, xb_D, xb_g;  // state boxes inside the active-set rounds (kernels_xbox.hip)
+  DevBuf jac_tmp;  // compact Jacobian records copied aside while they are expanded into the caller's fx / fu (QpSolve::densify)
   DevBuf m64[4];  // fp32-storage mode: fx, fu, Q, R widened for the paths that run the fp64 kernels
   // warm start: the early interior-point iterate (mu <= 0.5) remembered from the previous solve of the same shape
   DevBuf warmU, warm_llu, warm_luu, warm_llx, warm_lux;
@@ -161,6 +162,11 @@ struct pmpc_ctx {
   // outcome (the residual of this iteration and the linearisation of the next); spec_ok: that batch was the whole solve
   std::function<void()> post_batch;
   bool spec_fired = false, spec_ok = false;
+  // pmpc_scp_loop_device linearised the coming solve's Jacobians as compact records of this built-in model (jac_compact.h): they
+  // sit in this fx array and fu is stale.  The solve reads them as they are on the warm active-set path and expands them in place
+  // before anything else touches fx / fu (QpSolve::densify).  Null: fx / fu are the dense ABI stacks.
+  const double *jac_compact_fx = nullptr;
+  int jac_compact_model = 0;
 };
 
 namespace pmpc_impl {

@@ -95,6 +95,7 @@ class QpSolve {
   int setup_cones();
   void setup_keys();
   void reset_scalars();
+  void densify();
   void equality_solve();
   int finish(int status);
   int equality_phase();
@@ -137,6 +138,7 @@ int QpSolve::setup_workspace() {
   a.n = x + a.w;
   a.reg_x = p->reg_x; a.reg_u = p->reg_u;
   a.f = p->f; a.fx = p->fx; a.fu = p->fu; a.Q = p->Q; a.R = p->R;
+  a.jac_compact = (c->jac_compact_fx && c->jac_compact_fx == p->fx) ? 1 : 0;  // (the SCP loop linearised into compact records: densify())
   a.X_prev = p->X_prev; a.U_prev = p->U_prev; a.X_ref = p->X_ref; a.U_ref = p->U_ref;
   a.owner = (c->rank == 0);
   a.any_slew = (has_slew || has_slew0) ? 1 : 0;
@@ -237,6 +239,22 @@ void QpSolve::reset_scalars() {
   HIP_CHECK(hipMemsetAsync(w.fail.p, 0, sizeof(int), s));
   launch_ipm_exchange(0, false, false, sc, (const int *)w.fail.p, w.xch.d(), c->rank, c->world, nullptr, nullptr, nullptr, 0, s,
                       mu_target, w.part_dev.d());
+}
+
+// Compact Jacobian records (jac_compact.h) -> the dense fx / fu the ABI describes, in the caller's own arrays.  Only the sweeps of a warm
+// attempt of the active-set rounds (no rollout, Nc <= 1) read the records as they are; every other phase calls this first.  Rare (a solve
+// that leaves the warm path): the records are copied aside, then expanded — the dense stacks overlap them.
+void QpSolve::densify() {
+  if (!a.jac_compact) return;
+  ProfScope ps(c, 5);
+  const int model = c->jac_compact_model;
+  const size_t bytes = (size_t)jac_compact_doubles(model, N, M) * D8;
+  w.jac_tmp.ensure(bytes);
+  HIP_CHECK(hipMemcpyAsync(w.jac_tmp.p, p->fx, bytes, hipMemcpyDeviceToDevice, s));
+  launch_expand_jac(model, N, M, w.jac_tmp.d(), const_cast<double *>(p->fx), const_cast<double *>(p->fu), 0, s);
+  a.jac_compact = 0;
+  c->jac_compact_fx = nullptr;
+  if (verbose) printf("pmpc_hip: compact Jacobian records expanded (the solve left the warm active-set path)\n");
 }
 
 void QpSolve::equality_solve() {
@@ -612,6 +630,8 @@ int QpSolve::equality_phase() {
 // interior-point iterate (mode 1) or nothing (mode 2); 0 state boxes IGNORED (first phase of a cold start, see below); 2 on, nothing
 // stored.  mode 4: continue from the point an accepted attempt left in the output buffers (second phase of that cold start).
 int QpSolve::active_set_fast(double dual_scale, int mode, int max_rounds, int xb) {
+  // (compact Jacobian records serve the no-rollout warm start alone — as_start's use_defect —: every other start rolls out)
+  if (!(mode == 0 && as_defect_on && (p->flags & PMPC_PREV_IS_LAST_SOLUTION) && Nc <= 1)) densify();
   AsAttempt t = as_blocks(dual_scale, mode, max_rounds, xb);
   if (t.refused || !as_start(t)) return 1;
   as_rounds(t);
@@ -1350,6 +1370,7 @@ int QpSolve::run_cone_dispatch() {
       if (r == 0) return finish(0);
       if (verbose) printf("pmpc_hip: warm cone rounds not settled (%d): cold start\n", r);
     }
+    densify();
     if (f32) return PMPC_NEEDS_F64;
     if (cone_cold_rounds > 0) {
       if (r == 2) HIP_CHECK(hipMemsetAsync(w.fail.p, 0, sizeof(int), s));
@@ -1359,6 +1380,7 @@ int QpSolve::run_cone_dispatch() {
     }
     HIP_CHECK(hipMemsetAsync(w.fail.p, 0, sizeof(int), s));
   }
+  densify();
   if (f32) return PMPC_NEEDS_F64;
   if (ncones > 0) {  // the general form has no path-following fallback
     if (verbose) printf("pmpc_hip: stage cones (general form): the rounds did not settle\n");
@@ -1407,6 +1429,7 @@ int QpSolve::run_box_dispatch() {
     if (verbose) printf("pmpc_hip: warm active-set iteration not settled (%d): interior-point path\n", r);
     if (r == 2) HIP_CHECK(hipMemsetAsync(w.fail.p, 0, sizeof(int), s));
   }
+  densify();  // (nothing below reads compact Jacobian records)
   if (f32) return PMPC_NEEDS_F64;
   // Warm start (see below): when the previous solve of this shape ended in the interior-point phase, go there directly —
   // the equality-only solve (one factorisation + forward sweep) would only tell us that the boxes are active again; it
@@ -1461,6 +1484,7 @@ int QpSolve::run() {
   r = setup_cones();
   if (r != GO_ON) return r;
   setup_keys();
+  if (!fast || Nc > 1 || f32) densify();  // (the generic kernels' rounds and the condensing kernels read the dense stacks)
   return soc ? run_cone_dispatch() : run_box_dispatch();
 }
 

@@ -220,6 +220,27 @@ class DeviceSolver:
         self._after(wait_current_stream)
         return f, fx, fu
 
+    def linearize_compact(self, model: int, x0, X_prev, U_prev, params, wait_current_stream=True):
+        """f (dense) and the compact Jacobian records (one flat tensor) the SCP loop writes for its warm solves."""
+        M, N, x = X_prev.shape
+        f = torch.empty((M, N, x), dtype=torch.float64, device=X_prev.device)
+        jc = torch.empty((self.lib.pmpc_jac_compact_doubles(int(model), N, M),), dtype=torch.float64, device=X_prev.device)
+        self._before(wait_current_stream)
+        st = self.lib.pmpc_linearize_compact_device(self.h, int(model), N, M, _p(x0), _p(X_prev), _p(U_prev), _p(params), _p(f), _p(jc))
+        self._after(wait_current_stream)
+        assert st == 0, st
+        return f, jc
+
+    def expand_jac(self, model: int, jc, M: int, N: int, x: int, u: int, orient: int = 0, wait_current_stream=True):
+        """Dense (fx, fu) in ABI layout from compact records, read through their column- (0) or row-oriented (1) part."""
+        fx = torch.empty((M, N, x, x), dtype=torch.float64, device=jc.device)
+        fu = torch.empty((M, N, u, x), dtype=torch.float64, device=jc.device)
+        self._before(wait_current_stream)
+        st = self.lib.pmpc_expand_jac_device(self.h, int(model), N, M, _p(jc), _p(fx), _p(fu), int(orient))
+        self._after(wait_current_stream)
+        assert st == 0, st
+        return fx, fu
+
     def scp_residual(self, X, X_prev, U, U_prev, out=None, wait_current_stream=True):
         """max(max_ij ||X - X_prev||_2, max_ij ||U - U_prev||_2) of pmpc/scp_mpc.py:397-403 as a one-element device tensor
         (one fused pass on the solver's stream; inf if a trajectory holds a NaN)."""
