@@ -273,7 +273,10 @@ int pmpc_comm_world(pmpc_ctx *ctx);
 
 /* On-device dynamics linearisation (row a2 of SURVEY.md §8: the f_fx_fu_fn callback for the
  * built-in models).  model: 0 = unicycle (reference tests/dubins_car.py:48-90, params (3,M)),
- * 1 = synthetic quadrotor (params (4,M)).  X_prev/U_prev/x0 and outputs in ABI layout. */
+ * 1 = synthetic quadrotor (params (4,M) = [m, Jx, Jy, Jz]), 2 = kinematic bicycle, forward Euler: x = [px, py, theta, v],
+ * u = [a, delta] (acceleration, steering angle), params (2,M) = [L, dt] (wheelbase, step):
+ *   px+ = px + dt v cos(theta),  py+ = py + dt v sin(theta),  theta+ = theta + dt v tan(delta) / L,  v+ = v + dt a.
+ * Any other id: nothing is launched, the call returns 2.  X_prev/U_prev/x0 and outputs in ABI layout. */
 int pmpc_linearize_device(pmpc_ctx *ctx, int model, size_t N, size_t M, const double *x0, const double *X_prev,
                           const double *U_prev, const double *params, double *f, double *fx, double *fu);
 
@@ -311,7 +314,9 @@ int pmpc_scp_residual_device(pmpc_ctx *ctx, size_t xdim, size_t udim, size_t N, 
  *   res        device, `steps` doubles: the residual of each iteration (max over ranks when sharded)
  *   infos      host, `steps` entries (may be NULL)
  * The final iterate is in (X_out, U_out) if `steps` is odd, else in (X_prev, U_prev); *last_in_out says which.  Returns the
- * number of iterations completed (== steps unless a sub-problem failed: its status is in infos[returned]). */
+ * number of iterations completed (== steps unless a sub-problem failed: its status is in infos[returned]; an unknown model
+ * id fails the same way, before anything runs: 0, infos[0].status = 2).  The compact records are those of `model`: two models
+ * with the same dimensions (0 and 2) keep their own layouts on one context. */
 int pmpc_scp_loop_device(pmpc_ctx *ctx, int model, const double *params, const pmpc_problem *p, double *f2, double *fx2, double *fu2,
                          int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out);
 

@@ -150,6 +150,8 @@ def jac_live_mask(model: int, x: int, u: int):
     lib = load()
     mx, mu = np.zeros(x * x, dtype=np.uint8), np.zeros(x * u, dtype=np.uint8)
     got = lib.pmpc_jac_live_mask(int(model), mx.ctypes.data, mu.ctypes.data)
+    if got < 0:
+        raise ValueError(f"model {model} is not a built-in model")
     if got != 100 * x + u:
         raise ValueError(f"model {model}: compact records are for dims {got // 100} x {got % 100}, not {x} x {u}")
     return mx.reshape(x, x).T.astype(bool), mu.reshape(u, x).T.astype(bool)  # (column-major blocks)

@@ -7,6 +7,7 @@
 // model 0: unicycle of the reference's tests/dubins_car.py:48-90 (closed-form Jacobians; the
 //          reference uses torch.autograd, :11-30).  params (3,M) = [v_scale, w_scale, T].
 // model 1: synthetic quadrotor of SURVEY.md §8(d) (not in the reference). params (4,M) = [m,Jx,Jy,Jz].
+// model 2: kinematic bicycle, forward Euler (not in the reference).  x = [px, py, theta, v], u = [a, delta], params (2,M) = [L, dt].
 // Host (numpy) specifications: pmpc_amd/dynamics.py.  One thread evaluates one (particle, stage) into an LDS record
 // [f | fx | fu]; the workgroup then streams its records out: consecutive (particle, stage) units are consecutive
 // in all three stacks, so every store instruction writes 64 consecutive doubles (8-byte stores scattered inside each
@@ -30,6 +31,22 @@ struct Quadrotor {
   static __device__ __forceinline__ void eval(long long idx, int N, const double *x0, const double *X_prev, const double *U_prev,
                                               const double *params, double *fo, double *A, double *B);
 };
+
+struct Bicycle {
+  static constexpr int X = 4, U = 2, UNITS = 64;
+  typedef jacc::BicycleSpec Spec;
+  static __device__ __forceinline__ void eval(long long idx, int N, const double *x0, const double *X_prev, const double *U_prev,
+                                              const double *params, double *fo, double *A, double *B);
+};
+
+// one call site per model id: fn(Model{}); an id model_known() rejects never gets here (the entry points of solver.hip test it)
+template <class F>
+void with_model(int model, F &&fn) {
+  if (model == 0) fn(Unicycle{});
+  else if (model == 1) fn(Quadrotor{});
+  else if (model == 2) fn(Bicycle{});
+  else throw PmpcHipError{(int)hipErrorInvalidValue, "unknown built-in model", __FILE__, __LINE__};
+}
 
 __device__ __forceinline__ void Unicycle::eval(long long idx, int N, const double *x0, const double *X_prev, const double *U_prev,
                                                const double *params, double *fo, double *A, double *B) {
@@ -65,6 +82,28 @@ __device__ __forceinline__ void Unicycle::eval(long long idx, int N, const doubl
   B[0 + 4 * 1] = (dn1_du2 * iu22 - 2.0 * n1 * iu22 * iu2) * (-ws);
   B[1 + 4 * 1] = (dn2_du2 * iu22 - 2.0 * n2 * iu22 * iu2) * (-ws);
   B[3 + 4 * 1] = T * (-ws);
+}
+
+__device__ __forceinline__ void Bicycle::eval(long long idx, int N, const double *x0, const double *X_prev, const double *U_prev,
+                                              const double *params, double *fo, double *A, double *B) {
+  const int i = (int)(idx / N), j = (int)(idx % N);
+  const double *xs = j == 0 ? x0 + 4 * (size_t)i : X_prev + (idx - 1) * 4;
+  const double *us = U_prev + idx * 2, *p = params + 2 * (size_t)i;
+  const double Lw = p[0], dt = p[1];
+  const double px = xs[0], py = xs[1], th = xs[2], v = xs[3], acc = us[0];
+  double s, c;
+  sincos(th, &s, &c);
+  const double td = tan(us[1]), dtv = dt * v;
+  fo[0] = px + dtv * c; fo[1] = py + dtv * s; fo[2] = th + dtv * td / Lw; fo[3] = v + dt * acc;
+  // (A and B arrive zeroed; column-major blocks: A[r + 4*t] = dF_r/dx_t)
+  A[0 + 4 * 0] = 1.0; A[1 + 4 * 1] = 1.0; A[2 + 4 * 2] = 1.0; A[3 + 4 * 3] = 1.0;
+  A[0 + 4 * 2] = -dtv * s;
+  A[0 + 4 * 3] = dt * c;
+  A[1 + 4 * 2] = dtv * c;
+  A[1 + 4 * 3] = dt * s;
+  A[2 + 4 * 3] = dt * td / Lw;
+  B[3 + 4 * 0] = dt;
+  B[2 + 4 * 1] = dtv * (1.0 + td * td) / Lw;
 }
 
 __device__ __forceinline__ void Quadrotor::eval(long long idx, int N, const double *x0, const double *X_prev, const double *U_prev,
@@ -280,8 +319,7 @@ void launch_linearize(int model, int N, int M, const double *x0, const double *X
                       const double *params, double *f, double *fx, double *fu, hipStream_t s, int jac32) {
   ResArgs none;
   memset(&none, 0, sizeof(none));
-  if (model == 0) launch_model<Unicycle>(N, M, x0, X_prev, U_prev, params, f, fx, fu, none, s, jac32);
-  else launch_model<Quadrotor>(N, M, x0, X_prev, U_prev, params, f, fx, fu, none, s, jac32);
+  with_model(model, [&](auto m) { launch_model<decltype(m)>(N, M, x0, X_prev, U_prev, params, f, fx, fu, none, s, jac32); });
 }
 // compact variant: jc (the caller's fx scratch array) receives [M N records | M pools]; res_out null: no residual blocks
 void launch_linearize_compact(int model, int N, int M, const double *x0, const double *X_prev, const double *U_prev, const double *params,
@@ -294,21 +332,32 @@ void launch_linearize_compact(int model, int N, int M, const double *x0, const d
     r.nblk = (int)residual_blocks(r.rows);
     r.out_bits = (unsigned long long *)res_out;
   }
-  if (model == 0) launch_model_compact<Unicycle>(N, M, x0, X_prev, U_prev, params, f, jc, r, s);
-  else launch_model_compact<Quadrotor>(N, M, x0, X_prev, U_prev, params, f, jc, r, s);
+  with_model(model, [&](auto m) { launch_model_compact<decltype(m)>(N, M, x0, X_prev, U_prev, params, f, jc, r, s); });
 }
-bool jac_compact_dims(int model, int x, int u) { return model == 0 ? (x == Unicycle::X && u == Unicycle::U) : (model == 1 && x == Quadrotor::X && u == Quadrotor::U); }
+bool model_known(int model) { return model >= 0 && model <= 2; }
+bool jac_compact_dims(int model, int x, int u) {
+  bool ok = false;
+  if (model_known(model)) with_model(model, [&](auto m) { ok = x == decltype(m)::X && u == decltype(m)::U; });
+  return ok;
+}
 long long jac_compact_doubles(int model, int N, int M) {
   const long long tot = (long long)M * N;
-  return model == 0 ? tot * jacc::Compact<jacc::UnicycleSpec>::REC + (long long)M * jacc::Compact<jacc::UnicycleSpec>::POOL
-                    : tot * jacc::Compact<jacc::QuadrotorSpec>::REC + (long long)M * jacc::Compact<jacc::QuadrotorSpec>::POOL;
+  long long n = -1;
+  if (model_known(model))
+    with_model(model, [&](auto m) {
+      typedef jacc::Compact<typename decltype(m)::Spec> C;
+      n = tot * C::REC + (long long)M * C::POOL;
+    });
+  return n;
 }
 void launch_expand_jac(int model, int N, int M, const double *jc, double *fx, double *fu, int orient, hipStream_t s) {
   const long long tot = (long long)M * N;
-  long long b = (tot * (model == 0 ? 24 : 192) + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (model == 0) hipLaunchKernelGGL((k_expand_jac<Unicycle>), dim3((unsigned)b), dim3(256), 0, s, N, tot, jc, fx, fu, orient);
-  else hipLaunchKernelGGL((k_expand_jac<Quadrotor>), dim3((unsigned)b), dim3(256), 0, s, N, tot, jc, fx, fu, orient);
+  with_model(model, [&](auto m) {
+    typedef decltype(m) Model;
+    long long b = (tot * (Model::X * Model::X + Model::X * Model::U) + 255) / 256;
+    if (b > 8192) b = 8192;
+    hipLaunchKernelGGL((k_expand_jac<Model>), dim3((unsigned)b), dim3(256), 0, s, N, tot, jc, fx, fu, orient);
+  });
 }
 // which entries of fx (x*x, column-major) / fu (x*u, column-major) the compact records treat as live (1) — host-side, for the tests
 int jac_live_mask(int model, unsigned char *fx_mask, unsigned char *fu_mask) {
@@ -318,9 +367,9 @@ int jac_live_mask(int model, unsigned char *fx_mask, unsigned char *fu_mask) {
       for (int r = 0; r < C::X; r++) (c < C::X ? fx_mask[r + C::X * c] : fu_mask[r + C::X * (c - C::X)]) = C::cls(r, c) == -1;
     return C::X * 100 + C::U;
   };
-  if (model == 0) return fill(jacc::UnicycleSpec{});
-  if (model == 1) return fill(jacc::QuadrotorSpec{});
-  return -1;
+  int dims = -1;
+  if (model_known(model)) with_model(model, [&](auto m) { dims = fill(typename decltype(m)::Spec{}); });
+  return dims;
 }
 void launch_widen_f32(const float *src, double *dst, long long n, hipStream_t s) {
   long long b = (n + 255) / 256;
@@ -337,8 +386,7 @@ void launch_linearize_with_residual(int model, int N, int M, const double *x0, c
   r.X = Xr; r.Xp = Xrp; r.U = Ur; r.Up = Urp; r.rows = (long long)M * N; r.x = x; r.u = u;
   r.nblk = (int)residual_blocks(r.rows);
   r.out_bits = (unsigned long long *)res_out;
-  if (model == 0) launch_model<Unicycle>(N, M, x0, X_prev, U_prev, params, f, fx, fu, r, s, jac32);
-  else launch_model<Quadrotor>(N, M, x0, X_prev, U_prev, params, f, fx, fu, r, s, jac32);
+  with_model(model, [&](auto m) { launch_model<decltype(m)>(N, M, x0, X_prev, U_prev, params, f, fx, fu, r, s, jac32); });
 }
 
 // SCP residual of pmpc/scp_mpc.py:397-403: max over (particle, stage) of the 2-norms of X - X_prev and U - U_prev, in one

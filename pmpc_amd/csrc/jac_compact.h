@@ -25,7 +25,7 @@ namespace jacc {
 constexpr int NONE = -(1 << 30);  // lane map: this lane reads no Jacobian entry
 
 struct UnicycleSpec {
-  static constexpr int X = 4, U = 2;
+  static constexpr int X = 4, U = 2, MODEL = 0;  // MODEL: the id of the ABI (include/pmpc_abi.h)
   static constexpr const char *CONSTS = "1ab";  // 1, T v_scale, -T w_scale
   static constexpr const char *ROWS[4] = {
       "1.xx" "xx",
@@ -34,8 +34,18 @@ struct UnicycleSpec {
       "...1" ".b",
   };
 };
+struct BicycleSpec {
+  static constexpr int X = 4, U = 2, MODEL = 2;
+  static constexpr const char *CONSTS = "1d";  // 1, dt
+  static constexpr const char *ROWS[4] = {
+      "1.xx" "..",
+      ".1xx" "..",
+      "..1x" ".x",
+      "...1" "d.",
+  };
+};
 struct QuadrotorSpec {
-  static constexpr int X = 12, U = 4;
+  static constexpr int X = 12, U = 4, MODEL = 1;
   static constexpr const char *CONSTS = "1dabc";  // 1, dt, dt / Jx, dt / Jy, dt / Jz
   static constexpr const char *ROWS[12] = {
       "1..d........" "....",
@@ -153,9 +163,22 @@ struct Compact {
   static_assert(REC + POOL <= XX, "compact records must fit the fx scratch array for every horizon N >= 1");
 };
 
-// the model whose records a sweep instantiation (XD, UD) can read
-template <int XD, int UD> struct SpecFor { typedef void type; };
-template <> struct SpecFor<4, 2> { typedef UnicycleSpec type; };
-template <> struct SpecFor<12, 4> { typedef QuadrotorSpec type; };
+// The models whose records a sweep instantiation (XD, UD) can read: the dimensions do not name the model, LQArgs::jac_compact does
+// (model id + 1).  select() gives a lane its entries of the three maps and the record / pool sizes of the candidate with that id —
+// one uniform branch per further candidate, in the prologue of the sweep; a pair with one candidate takes it without a test.
+template <class... S> struct SpecList { static constexpr int COUNT = sizeof...(S); };
+template <int XD, int UD> struct SpecFor { typedef SpecList<> list; };
+template <> struct SpecFor<4, 2> { typedef SpecList<UnicycleSpec, BicycleSpec> list; };
+template <> struct SpecFor<12, 4> { typedef SpecList<QuadrotorSpec> list; };
+
+struct LaneSel { int bwd, fwdA, fwdB, rec, pool; };
+template <class S0, class... S>
+__device__ __forceinline__ LaneSel select(SpecList<S0, S...>, int tag, int lane) {
+  if constexpr (sizeof...(S) > 0) {
+    if (tag != S0::MODEL + 1) return select(SpecList<S...>{}, tag, lane);
+  }
+  typedef Compact<S0> C;
+  return {C::tab.bwd[lane], C::tab.fwdA[lane], C::tab.fwdB[lane], C::REC, C::POOL};
+}
 
 }  // namespace jacc

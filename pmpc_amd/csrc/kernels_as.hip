@@ -140,14 +140,15 @@ __global__ void __launch_bounds__(64, MODE == 2 ? 2 : (MODE == 1 ? PMPC_AS_DEEP_
   int sF = fF ? -(int)MB * (L.cxv ? XD * XD : XD * UD) : 0;
   // compact records (jac_compact.h): the same triple from the unit's record (stage stride = record size) or, when it holds no
   // live entry, from the particle's constant pool (stage stride 0) — the lane map is a compile-time table, the stages see no change
-  typedef typename jacc::SpecFor<XD, UD>::type JSpec;
-  if constexpr (!std::is_void<JSpec>::value && std::is_same<MT, double>::value) {
+  // The record layout is the MODEL's (a.jac_compact = model id + 1), not the dimensions': jacc::select picks it, here in the prologue only.
+  typedef typename jacc::SpecFor<XD, UD>::list JSpecs;
+  if constexpr (JSpecs::COUNT > 0 && std::is_same<MT, double>::value) {
     if (a.jac_compact) {
-      typedef jacc::Compact<JSpec> JC;
-      const int m = JC::tab.bwd[lane];
+      const jacc::LaneSel js = jacc::select(JSpecs{}, a.jac_compact, lane);
+      const int m = js.bwd;
       if (m != jacc::NONE) {
-        pF = m >= 0 ? (const MT *)a.fx + (pbase + jtop) * JC::REC + m : (const MT *)a.fx + (size_t)a.M * N * JC::REC + (size_t)i * JC::POOL + (-1 - m);
-        sF = m >= 0 ? -(int)MB * JC::REC : 0;
+        pF = m >= 0 ? (const MT *)a.fx + (pbase + jtop) * js.rec + m : (const MT *)a.fx + (size_t)a.M * N * js.rec + (size_t)i * js.pool + (-1 - m);
+        sF = m >= 0 ? -(int)MB * js.rec : 0;
       }
     }
   }
@@ -597,16 +598,17 @@ __global__ void __launch_bounds__(64, 4) k_fwd_as(LQArgs a) {
     pA = (const char *)((const MT *)a.K + pbase * 64 + 16 * L.cb + g);
     sAr = 4 * MB; sAj = 64 * MB;
   }
-  typedef typename jacc::SpecFor<XD, UD>::type JSpec;
-  if constexpr (!std::is_void<JSpec>::value && std::is_same<MT, double>::value) {
-    // compact records (jac_compact.h): the row triple is KS consecutive doubles of the unit's record, or of the particle's constant pool
+  typedef typename jacc::SpecFor<XD, UD>::list JSpecs;
+  if constexpr (JSpecs::COUNT > 0 && std::is_same<MT, double>::value) {
+    // compact records (jac_compact.h): the row triple is KS consecutive doubles of the unit's record, or of the particle's constant pool;
+    // the layout is that of the model a.jac_compact names (id + 1)
     if (a.jac_compact && L.cxv) {
-      typedef jacc::Compact<JSpec> JC;
-      const double *rec = a.fx + pbase * JC::REC, *pool = a.fx + (size_t)a.M * N * JC::REC + (size_t)i * JC::POOL;
-      const int mA = JC::tab.fwdA[lane], mB = JC::tab.fwdB[lane];
+      const jacc::LaneSel js = jacc::select(JSpecs{}, a.jac_compact, lane);
+      const double *rec = a.fx + pbase * js.rec, *pool = a.fx + (size_t)a.M * N * js.rec + (size_t)i * js.pool;
+      const int mA = js.fwdA, mB = js.fwdB;
       pA = (const char *)(mA >= 0 ? rec + mA : pool + (-1 - mA));
-      sAr = MB; sAj = mA >= 0 ? JC::REC * MB : 0;
-      if (gu) { pB = (const char *)(mB >= 0 ? rec + mB : pool + (-1 - mB)); sBj = mB >= 0 ? JC::REC * MB : 0; }
+      sAr = MB; sAj = mA >= 0 ? js.rec * MB : 0;
+      if (gu) { pB = (const char *)(mB >= 0 ? rec + mB : pool + (-1 - mB)); sBj = mB >= 0 ? js.rec * MB : 0; }
     }
   }
   bool vA[KS];  // (padding: state column KS g + r beyond xdim -> zero; the record holds zeros there already)

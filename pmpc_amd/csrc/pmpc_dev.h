@@ -153,8 +153,8 @@ struct LQArgs {
   // cost and a gradient term, per state entry (M,N,x).  Null = none (the XBOX instantiations are not launched).
   const double *xb_D, *xb_g;
   int mat32;       // fx, fu, Q, R (and the factor record a.K of the active-set sweeps) are FLOAT arrays (fp32-storage mode; kernels_as.hip only)
-  int jac_compact; // fx holds the compact Jacobian records of the built-in model with these dims ([M N records | M pools], jac_compact.h) and fu is
-                   // not read (active-set sweeps of kernels_as.hip with Nc <= 1, fp64 storage only; set by the SCP loop's warm solves)
+  int jac_compact; // non-zero: fx holds the compact Jacobian records of built-in model `jac_compact - 1` ([M N records | M pools], jac_compact.h —
+                   // the sweeps take the lane map of THAT model, two models may share their dimensions) and fu is not read (active-set sweeps of kernels_as.hip with Nc <= 1, fp64 storage only; set by the SCP loop's warm solves)
   int owner;       // this rank holds global particle 0 (whose bounds the consensus controls use)
   int any_slew;    // slew_reg or slew_reg0 present
   int sym_cost;    // caller guarantees Q_j = Q_j', R_j = R_j' (else OSQP's triu semantics need the generic path)
@@ -410,8 +410,9 @@ void launch_linearize(int model, int N, int M, const double *x0, const double *X
 void launch_linearize_compact(int model, int N, int M, const double *x0, const double *X_prev, const double *U_prev, const double *params,
                               double *f, double *jc, const double *Xr, const double *Xrp, const double *Ur, const double *Urp, int x, int u,
                               double *res_out, hipStream_t s);
+bool model_known(int model);                              // a built-in model id (include/pmpc_abi.h)
 bool jac_compact_dims(int model, int x, int u);           // the model has compact records and (x, u) are its dimensions
-long long jac_compact_doubles(int model, int N, int M);  // size of jc
+long long jac_compact_doubles(int model, int N, int M);  // size of jc (-1: unknown model)
 void launch_expand_jac(int model, int N, int M, const double *jc, double *fx, double *fu, int orient, hipStream_t s);  // jc must not overlap fx / fu
 int jac_live_mask(int model, unsigned char *fx_mask, unsigned char *fu_mask);
 void launch_linearize_with_residual(int model, int N, int M, const double *x0, const double *X_prev, const double *U_prev,

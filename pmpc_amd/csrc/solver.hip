@@ -503,6 +503,7 @@ int pmpc_linearize_device_f32(pmpc_ctx *c, int model, size_t N, size_t M, const 
                               const double *U_prev, const double *params, double *f, float *fx, float *fu) {
   try {
     HIP_CHECK(hipSetDevice(c->device));
+    if (!model_known(model)) return 2;
     ProfScope ps(c, 6);
     launch_linearize(model, (int)N, (int)M, x0, X_prev, U_prev, params, f, (double *)fx, (double *)fu, c->stream, 1);
     HIP_CHECK(hipGetLastError());
@@ -516,6 +517,7 @@ int pmpc_linearize_device(pmpc_ctx *c, int model, size_t N, size_t M, const doub
                           const double *U_prev, const double *params, double *f, double *fx, double *fu) {
   try {
     HIP_CHECK(hipSetDevice(c->device));
+    if (!model_known(model)) return 2;
     ProfScope ps(c, 6);
     launch_linearize(model, (int)N, (int)M, x0, X_prev, U_prev, params, f, fx, fu, c->stream);
     HIP_CHECK(hipGetLastError());
@@ -532,7 +534,7 @@ int pmpc_linearize_compact_device(pmpc_ctx *c, int model, size_t N, size_t M, co
                                   const double *params, double *f, double *jc) {
   try {
     HIP_CHECK(hipSetDevice(c->device));
-    if (model < 0 || model > 1) return 2;
+    if (!model_known(model)) return 2;
     ProfScope ps(c, 6);
     launch_linearize_compact(model, (int)N, (int)M, x0, X_prev, U_prev, params, f, jc, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream);
     HIP_CHECK(hipGetLastError());
@@ -544,7 +546,7 @@ int pmpc_linearize_compact_device(pmpc_ctx *c, int model, size_t N, size_t M, co
 int pmpc_expand_jac_device(pmpc_ctx *c, int model, size_t N, size_t M, const double *jc, double *fx, double *fu, int orient) {
   try {
     HIP_CHECK(hipSetDevice(c->device));
-    if (model < 0 || model > 1) return 2;
+    if (!model_known(model)) return 2;
     launch_expand_jac(model, (int)N, (int)M, jc, fx, fu, orient, c->stream);
     HIP_CHECK(hipGetLastError());
   } catch (const PmpcHipError &) {
@@ -552,7 +554,7 @@ int pmpc_expand_jac_device(pmpc_ctx *c, int model, size_t N, size_t M, const dou
   }
   return 0;
 }
-long long pmpc_jac_compact_doubles(int model, size_t N, size_t M) { return (model < 0 || model > 1) ? -1 : jac_compact_doubles(model, (int)N, (int)M); }
+long long pmpc_jac_compact_doubles(int model, size_t N, size_t M) { return model_known(model) ? jac_compact_doubles(model, (int)N, (int)M) : -1; }
 int pmpc_jac_live_mask(int model, unsigned char *fx_mask, unsigned char *fu_mask) { return jac_live_mask(model, fx_mask, fu_mask); }
 
 // -------------------------------------------------------------------------------------------------
@@ -727,6 +729,11 @@ int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmp
                           c->opt[OPT_AS_WARM] != 0.0 && c->opt[OPT_POLISH_MU] > 0.0;
   bool compact_set[2] = {false, false};  // what the linearisation buffer sets hold
   int done = 0, cur = 0;
+  if (!model_known(model)) {  // nothing runs (the kernels of some other model would read the caller's arrays with ITS dimensions)
+    if (infos && steps > 0) { memset(&infos[0], 0, sizeof(pmpc_info)); infos[0].status = 2; }
+    if (last_in_out) *last_in_out = 0;
+    return 0;
+  }
   bool lin_ready = false;  // the linearisation of iteration `done` is already enqueued (valid speculation of the previous one)
   try {
     HIP_CHECK(hipSetDevice(c->device));

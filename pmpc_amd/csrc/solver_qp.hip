@@ -138,7 +138,7 @@ int QpSolve::setup_workspace() {
   a.n = x + a.w;
   a.reg_x = p->reg_x; a.reg_u = p->reg_u;
   a.f = p->f; a.fx = p->fx; a.fu = p->fu; a.Q = p->Q; a.R = p->R;
-  a.jac_compact = (c->jac_compact_fx && c->jac_compact_fx == p->fx) ? 1 : 0;  // (the SCP loop linearised into compact records: densify())
+  a.jac_compact = (c->jac_compact_fx && c->jac_compact_fx == p->fx) ? c->jac_compact_model + 1 : 0;  // (the SCP loop linearised into compact records of that model: densify())
   a.X_prev = p->X_prev; a.U_prev = p->U_prev; a.X_ref = p->X_ref; a.U_ref = p->U_ref;
   a.owner = (c->rank == 0);
   a.any_slew = (has_slew || has_slew0) ? 1 : 0;

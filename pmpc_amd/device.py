@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 
-MODEL_UNICYCLE, MODEL_QUADROTOR = 0, 1
+MODEL_UNICYCLE, MODEL_QUADROTOR, MODEL_BICYCLE = 0, 1, 2
 
 
 def _p(t: Optional[torch.Tensor], dtype=torch.float64):
@@ -212,19 +212,24 @@ class DeviceSolver:
         fu = torch.empty((M, N, u, x), dtype=torch.float64, device=dev) if fu is None else fu
         self._before(wait_current_stream)
         if fx.dtype == torch.float32:  # fp32-storage mode: the Jacobian stacks are written as float32
-            self.lib.pmpc_linearize_device_f32(self.h, int(model), N, M, _p(x0), _p(X_prev), _p(U_prev), _p(params), _p(f), _p(fx, torch.float32),
+            st = self.lib.pmpc_linearize_device_f32(self.h, int(model), N, M, _p(x0), _p(X_prev), _p(U_prev), _p(params), _p(f), _p(fx, torch.float32),
                                                _p(fu, torch.float32))
         else:
-            self.lib.pmpc_linearize_device(self.h, int(model), N, M, _p(x0), _p(X_prev), _p(U_prev), _p(params), _p(f), _p(fx),
+            st = self.lib.pmpc_linearize_device(self.h, int(model), N, M, _p(x0), _p(X_prev), _p(U_prev), _p(params), _p(f), _p(fx),
                                            _p(fu))
         self._after(wait_current_stream)
+        if st != 0:
+            raise RuntimeError(f"pmpc_linearize_device failed ({st}): model {model} is not a built-in model, or a HIP error")
         return f, fx, fu
 
     def linearize_compact(self, model: int, x0, X_prev, U_prev, params, wait_current_stream=True):
         """f (dense) and the compact Jacobian records (one flat tensor) the SCP loop writes for its warm solves."""
         M, N, x = X_prev.shape
         f = torch.empty((M, N, x), dtype=torch.float64, device=X_prev.device)
-        jc = torch.empty((self.lib.pmpc_jac_compact_doubles(int(model), N, M),), dtype=torch.float64, device=X_prev.device)
+        n = self.lib.pmpc_jac_compact_doubles(int(model), N, M)
+        if n < 0:
+            raise RuntimeError(f"model {model} is not a built-in model")
+        jc = torch.empty((n,), dtype=torch.float64, device=X_prev.device)
         self._before(wait_current_stream)
         st = self.lib.pmpc_linearize_compact_device(self.h, int(model), N, M, _p(x0), _p(X_prev), _p(U_prev), _p(params), _p(f), _p(jc))
         self._after(wait_current_stream)

@@ -12,6 +12,9 @@ Jacobians, in the reference's `f_fx_fu_fn(X, U) -> f, fx, fu` contract
 * `quadrotor` — the synthetic 12-state / 4-control rigid body of SURVEY.md §8(d) (NOT in the
   reference): x = [p(3), v(3), rpy(3), w(3)], u = [T, tx, ty, tz], explicit Euler, dt = 0.05.
 
+* `bicycle`   — the kinematic bicycle (NOT in the reference): x = [px, py, theta, v], u = [a, delta], p = [L, dt],
+  forward Euler; checked against complex-step differentiation of its own `f` in tests/test_bicycle_model.py.
+
 These are the specifications the on-device linearisation kernels (csrc/dynamics.hip) follow.
 """
 from __future__ import annotations
@@ -106,6 +109,56 @@ def unicycle_torch(x, u, p, eps=1e-6):
     fu[..., 0, 1] = (dn1_du2 * iu22 - 2.0 * n1 * iu22 * iu2) * (-ws)
     fu[..., 1, 1] = (dn2_du2 * iu22 - 2.0 * n2 * iu22 * iu2) * (-ws)
     fu[..., 3, 1] = T * (-ws)
+    return f, fx, fu
+
+
+# -------------------------------------------------------------------------------------------------
+# kinematic bicycle, forward Euler (built-in model 2)
+# -------------------------------------------------------------------------------------------------
+def bicycle(x, u, p):
+    """x (...,4) = [px, py, theta, v]; u (...,2) = [a, delta] (acceleration, steering angle); p (...,2) = [L, dt]
+    (wheelbase, step).  Complex inputs are kept complex (complex-step differentiation of `f`)."""
+    num = lambda a: np.asarray(a, complex if np.iscomplexobj(a) else float)
+    x, u, p = num(x), num(u), num(p)
+    L, dt = p[..., 0], p[..., 1]
+    px, py, th, v = x[..., 0], x[..., 1], x[..., 2], x[..., 3]
+    acc, td = u[..., 0], np.tan(u[..., 1])
+    s, c = np.sin(th), np.cos(th)
+    dtv = dt * v
+    f = np.stack([px + dtv * c, py + dtv * s, th + dtv * td / L, v + dt * acc], -1)
+    shp = f.shape[:-1]
+    fx = np.zeros(shp + (4, 4), dtype=f.dtype)
+    fu = np.zeros(shp + (4, 2), dtype=f.dtype)
+    for k in range(4):
+        fx[..., k, k] = 1.0
+    fx[..., 0, 2] = -dtv * s
+    fx[..., 0, 3] = dt * c
+    fx[..., 1, 2] = dtv * c
+    fx[..., 1, 3] = dt * s
+    fx[..., 2, 3] = dt * td / L
+    fu[..., 3, 0] = dt
+    fu[..., 2, 1] = dtv * (1.0 + td * td) / L  # sec^2 = 1 + tan^2
+    return f, fx, fu
+
+
+def bicycle_torch(x, u, p):
+    """`bicycle` on torch tensors of any device — an `f_fx_fu_fn` body for the device-resident loop `solve(..., device="cuda")`."""
+    import torch
+
+    L, dt = p[..., 0], p[..., 1]
+    px, py, th, v = x[..., 0], x[..., 1], x[..., 2], x[..., 3]
+    acc, td = u[..., 0], torch.tan(u[..., 1])
+    s, c = torch.sin(th), torch.cos(th)
+    dtv = dt * v
+    f = torch.stack([px + dtv * c, py + dtv * s, th + dtv * td / L, v + dt * acc], -1)
+    fx = torch.zeros(f.shape[:-1] + (4, 4), dtype=f.dtype, device=f.device)
+    fu = torch.zeros(f.shape[:-1] + (4, 2), dtype=f.dtype, device=f.device)
+    fx[..., 0, 0] = fx[..., 1, 1] = fx[..., 2, 2] = fx[..., 3, 3] = 1.0
+    fx[..., 0, 2], fx[..., 0, 3] = -dtv * s, dt * c
+    fx[..., 1, 2], fx[..., 1, 3] = dtv * c, dt * s
+    fx[..., 2, 3] = dt * td / L
+    fu[..., 3, 0] = dt
+    fu[..., 2, 1] = dtv * (1.0 + td * td) / L
     return f, fx, fu
 
 
@@ -234,6 +287,47 @@ def make_quadrotor_problem(M=1024, N=50, seed=2020, Nc=1):
 
     def f_fx_fu_fn(X, U):
         return quadrotor(X, U, pp)
+
+    prob["f_fx_fu_fn"] = f_fx_fu_fn
+    prob["params"] = p
+    return prob
+
+
+BICYCLE_DT = 0.1
+
+
+def make_bicycle_problem(M=256, N=30, seed=2020, Nc=1):
+    """Lane change: every particle drives along +x at about 5 m/s and is asked to move over to a lane `w` to the left (its own
+    w around 2 m) a third of the way into the horizon; |a| <= 2, |delta| <= 0.5, wheelbase L = 2.7 m +- 10 % per particle."""
+    rng = np.random.default_rng(seed)
+    xdim, udim, dt = 4, 2, BICYCLE_DT
+    L = 2.7 * (1 + rng.uniform(-0.1, 0.1, M))
+    p = np.stack([L, np.full(M, dt)], -1)
+    v0 = 5.0 + 0.25 * rng.standard_normal(M)
+    x0 = np.zeros((M, xdim))
+    x0[:, 1] = 0.05 * rng.standard_normal(M)
+    x0[:, 2] = 0.02 * rng.standard_normal(M)
+    x0[:, 3] = v0
+    w = 2.0 + 0.2 * rng.standard_normal(M)
+    t = dt * np.arange(1, N + 1)
+    X_ref = np.zeros((M, N, xdim))
+    X_ref[..., 0] = x0[:, None, 0] + v0[:, None] * t[None, :]
+    X_ref[..., 1] = np.where(np.arange(N)[None, :] >= N // 3, w[:, None], 0.0)
+    X_ref[..., 3] = v0[:, None]
+    Q = np.tile(np.diag([1.0, 10.0, 1.0, 1.0]), (M, N, 1, 1))
+    R = np.tile(np.diag([0.1, 1.0]), (M, N, 1, 1))
+    X_prev = np.tile(x0[:, None, :], (1, N, 1))
+    X_prev[..., 0] = X_ref[..., 0]  # start iterate: straight on at the initial speed
+    bound = np.array([2.0, 0.5])
+    prob = dict(
+        x0=x0, Q=Q, R=R, X_ref=X_ref, U_ref=np.zeros((M, N, udim)), X_prev=X_prev, U_prev=np.zeros((M, N, udim)),
+        u_l=np.tile(-bound, (M, N, 1)), u_u=np.tile(bound, (M, N, 1)), reg_x=1.0, reg_u=1.0,
+        solver_settings=dict(solver="osqp", Nc=Nc),
+    )
+    pp = p[:, None, :]
+
+    def f_fx_fu_fn(X, U):
+        return bicycle(X, U, pp)
 
     prob["f_fx_fu_fn"] = f_fx_fu_fn
     prob["params"] = p

@@ -6,7 +6,7 @@
 contract, README.md:136-145 / scp_mpc.py:338-342) and returns `f (M,N,x)`, `fx (M,N,x,x)`, `fu (M,N,x,u)` as torch GPU
 tensors in the usual (row, col) layout — or already in the ABI layout `(M,N,col,row)` with `jacobians_abi_layout=True`,
 which saves one transposing copy of the Jacobian stacks per iteration.  A built-in model (`builtin_model="unicycle" |
-"quadrotor"`, `params=...`) is linearised by the HIP kernel of csrc/dynamics.hip instead of a Python callable.
+"quadrotor" | "bicycle"`, `params=...`) is linearised by the HIP kernel of csrc/dynamics.hip instead of a Python callable.
 Nothing crosses PCIe inside the loop except the scalars of the `hist` row (one small read per SCP iteration).
 
 `solver_settings["extra_cstrs"]` in the reference's tuple format is accepted for that case (pmpc_amd/extra_cstrs.py).
@@ -25,10 +25,10 @@ from typing import Any, Callable, Dict, Optional
 import numpy as np
 import torch
 
-from .device import MODEL_QUADROTOR, MODEL_UNICYCLE, DeviceSolver
+from .device import MODEL_BICYCLE, MODEL_QUADROTOR, MODEL_UNICYCLE, DeviceSolver
 from .utils import TablePrinter
 
-_MODELS = {"unicycle": MODEL_UNICYCLE, "quadrotor": MODEL_QUADROTOR}
+_MODELS = {"unicycle": MODEL_UNICYCLE, "quadrotor": MODEL_QUADROTOR, "bicycle": MODEL_BICYCLE}
 _solvers: Dict[int, DeviceSolver] = {}
 
 
@@ -87,7 +87,7 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
     s = solver or _solver_for(dev)
     model = _MODELS[builtin_model] if builtin_model is not None else None
     if model is not None:
-        assert params is not None, "builtin_model needs `params` (M, 3) unicycle / (M, 4) quadrotor"
+        assert params is not None, "builtin_model needs `params` (M, 3) unicycle / (M, 4) quadrotor / (M, 2) bicycle"
         params = T(params).reshape(M, -1).contiguous()
     x0c = x0.contiguous()
     soc_kw = {}
