@@ -296,6 +296,14 @@ int pmpc_expand_jac_device(pmpc_ctx *ctx, int model, size_t N, size_t M, const d
 long long pmpc_jac_compact_doubles(int model, size_t N, size_t M);
 int pmpc_jac_live_mask(int model, unsigned char *fx_mask, unsigned char *fu_mask);
 
+/* Which kernel variant an active-set sweep launch would take (pmpc_amd/csrc/as_variant.h) — host only, no device needed; for tests.
+ * sweep 0: factor sweep, out[0..4] = {mode, skip, defect, ex, f32}; sweep 1: forward sweep, out[0..4] = {defect, pf2, cone, f32, sens}.
+ * flags: which LQArgs fields the launch has set — bit 0 defect, 1 as_settled_in, 2 mat32, 3 cone_H, 4 xb_D, 5 as_uraw, 6 as_T.
+ * knobs: {deep2_maxm, deep_maxm, fwd_pf2_maxm}, null = the defaults (the environment is not read).  out[5..7]: whether (xdim, udim)
+ * has fp32-storage / cone / state-box sweeps at all (what the solver asks before it sets mat32 / cone_H, as_uraw / xb_D).
+ * Returns 1 if the variant is compiled for (xdim, udim), 0 if not, -1 if the pair has no active-set sweeps. */
+int pmpc_as_sweep_variant(int sweep, int xdim, int udim, int M, int Nc, unsigned flags, const int *knobs, int *out);
+
 /* SCP residual of one iteration (pmpc/scp_mpc.py:397-403): *out (device, one double) = max over particles and stages of
  * ||X - X_prev||_2 and ||U - U_prev||_2 (inf if a trajectory holds a NaN); asynchronous on pmpc_stream(). */
 int pmpc_scp_residual_device(pmpc_ctx *ctx, size_t xdim, size_t udim, size_t N, size_t M, const double *X, const double *X_prev,

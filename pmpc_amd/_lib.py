@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "pmpc_scp_residual_device", "pmpc_profile_read_partial", "pmpc_profile_read_all", "pmpc_scp_loop_device", "pmpc_linearize_device_f32",
     "pmpc_set_option", "pmpc_get_option", "pmpc_abi_struct_sizes", "pmpc_lcone_solve_host_ex", "pmpc_restart_stats",
     "pmpc_linearize_compact_device", "pmpc_expand_jac_device", "pmpc_jac_compact_doubles", "pmpc_jac_live_mask",
+    "pmpc_as_sweep_variant",
 ]
 
 
@@ -113,6 +114,9 @@ def load():
         lib.pmpc_jac_compact_doubles.restype = ctypes.c_longlong
         lib.pmpc_jac_live_mask.argtypes = [ctypes.c_int, vp, vp]
         lib.pmpc_jac_live_mask.restype = ctypes.c_int
+    if hasattr(lib, "pmpc_as_sweep_variant"):  # (likewise)
+        lib.pmpc_as_sweep_variant.argtypes = [ctypes.c_int] * 5 + [ctypes.c_uint, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+        lib.pmpc_as_sweep_variant.restype = ctypes.c_int
     lib.pmpc_scp_residual_device.argtypes = [vp, sz, sz, sz, sz] + [vp] * 5
     lib.pmpc_scp_residual_device.restype = ctypes.c_int
     lib.pmpc_profile_enable.argtypes = [vp, ctypes.c_int]
@@ -155,6 +159,23 @@ def jac_live_mask(model: int, x: int, u: int):
     if got != 100 * x + u:
         raise ValueError(f"model {model}: compact records are for dims {got // 100} x {got % 100}, not {x} x {u}")
     return mx.reshape(x, x).T.astype(bool), mu.reshape(u, x).T.astype(bool)  # (column-major blocks)
+
+
+AS_SWEEP_FLAGS = ("defect", "as_settled_in", "mat32", "cone_H", "xb_D", "as_uraw", "as_T")  # bit k of `flags` below
+
+
+def as_sweep_variant(sweep: str, x: int, u: int, M: int, Nc: int, flags: int, knobs=None):
+    """(variant, compiled, dims): the template arguments the launcher of the active-set factor ("bwd") / forward ("fwd") sweep would
+    pick (pmpc_amd/csrc/as_variant.h) as a tuple — bwd (mode, skip, defect, ex, f32), fwd (defect, pf2, cone, f32, sens) —, whether
+    that instantiation exists for (x, u), and whether the pair has (fp32-storage, cone, state-box) sweeps at all.  knobs:
+    (deep2_maxm, deep_maxm, fwd_pf2_maxm), None = the defaults.  Host only."""
+    lib = load()
+    out = (ctypes.c_int * 8)()
+    kn = (ctypes.c_int * 3)(*knobs) if knobs is not None else None
+    got = lib.pmpc_as_sweep_variant({"bwd": 0, "fwd": 1}[sweep], x, u, M, Nc, flags, kn, out)
+    if got < 0:
+        raise ValueError(f"({x}, {u}) is not a compiled pair of the active-set sweeps")
+    return tuple(out[:5]), bool(got), tuple(bool(v) for v in out[5:8])
 
 
 def dptr(a: np.ndarray):

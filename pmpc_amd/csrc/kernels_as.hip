@@ -22,6 +22,8 @@
 
 #include "fast_common.h"
 #include "as_ctl_dev.h"
+#include "as_variant.h"
+#include "../../include/pmpc_abi.h"
 #include "jac_compact.h"
 
 // Diagnostic build only (-DPMPC_STAGE_TIMELINE, tools/micro/stage_timeline.py; never in the shipped library): s_memtime stamps at the
@@ -51,22 +53,16 @@ __device__ unsigned long long pmpc_tl[3][128][PMPC_TL_STAMPS];  // [0 full facto
                                  // the later rounds always use it); 0: never.  Since the merged loads (13 memory instructions per
                                  // stage) its three register sets fit: 166 - 185 registers, no scratch
 #endif
-#ifndef PMPC_AS_PINGPONG
-#define PMPC_AS_PINGPONG 0    // main loop: two stages per trip, the prefetch register sets swap roles (0: one stage + rotation moves)
-#endif
-#ifndef PMPC_AS_DEFECT_G
-#define PMPC_AS_DEFECT_G 0    // DEFECT sweeps: the defect term of the gradient as G'r from the product G = S F the stage forms anyway
-                              // (3 multiply-adds on a row-distributed copy of r) instead of S r by 3 row sums over DPP moves (39 instructions)
-#endif
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------
 // backward (factor) sweep of an active-set round
 // ------------------------------------------------------------------------------------------------
-// Loop structure: the free stages j >= 1 (the bulk of the horizon) run in a branch-free MAIN body, two stages per loop trip
-// with the two prefetch register sets swapping roles (no rotation moves); the consensus stages and stage 0 (no incoming
-// state) go through the general body afterwards.
+// Loop structure: the free stages j >= 1 (the bulk of the horizon) run in a branch-free MAIN body, one stage per loop trip:
+// the stage works on prefetch register set A while the next stage's data lands in B, then A = B (deep2: a ring of three sets,
+// three stages per trip, rotated by moves over the last stages only); the consensus stages and stage 0 (no incoming state) go
+// through the general body afterwards.
 // MODE — how far ahead a stage's data is requested:
 //   0 lean   early data (F, R, control word, f) one stage ahead, mid / late data (Q, base state below) behind the Cholesky phase of the
 //            stage above: <= 128 registers, 4 waves per SIMD (more than 3072 particles per GPU: the waves hide each other's latency)
@@ -350,26 +346,18 @@ __global__ void __launch_bounds__(64, MODE == 2 ? 2 : (MODE == 1 ? PMPC_AS_DEEP_
     if (MODE != 2 && below) fetch_early(j - 1, nxt);  // (deep2: the caller's ring has requested stage j - 2 already)
     TL(2);  // next stage's loads issued
 
-    double d_row[KS];
     if (DEFECT) {  // x_j = F [x_{j-1}; u_j] + r_j: the cost-to-go gradient seen through the stage is s + S r
-      if (PMPC_AS_DEFECT_G) {
-        col_to_row<KS>(df_c, g, d_row);  // h = F'(s + S r) = F's + G'r with G = S F: the S r product is never formed
-      } else {
 #pragma unroll
-        for (int r = 0; r < KS; r++) s_row[r] += row_allsum(S[r] * df_c);
-      }
+      for (int r = 0; r < KS; r++) s_row[r] += row_allsum(S[r] * df_c);
     }
     // ---- h = F' s (+ control gradient) -----------------------------------------------------------------
     double hp = fma(Rc, um_g, gu_c);
 #pragma unroll
     for (int r = 0; r < KS; r++) hp = fma(Fr[r], s_row[r], hp);
-    double h_col = 0.0;
+    const double h_col = grp_allsum(hp);
     double hu[UD];
-    if (!(DEFECT && PMPC_AS_DEFECT_G)) {
-      h_col = grp_allsum(hp);
 #pragma unroll
-      for (int b = 0; b < UD; b++) hu[b] = readlane_d(h_col, XP + b);
-    }
+    for (int b = 0; b < UD; b++) hu[b] = readlane_d(h_col, XP + b);
 
     TL(3);  // gradient h = F' (s + S r) formed, control rows read out
     // ---- H = F' S F + blkdiag(Q~_{j-1}, R~_j) ------------------------------------------------------
@@ -390,13 +378,6 @@ __global__ void __launch_bounds__(64, MODE == 2 ? 2 : (MODE == 1 ? PMPC_AS_DEEP_
     for (int r = 0; r < KS; r++) G = mfma(S[r], Fr[r], G);
 #pragma unroll
     for (int r = 0; r < KS; r++) H = mfma(Fr[r], G[r], H);
-    if (DEFECT && PMPC_AS_DEFECT_G) {
-#pragma unroll
-      for (int r = 0; r < KS; r++) hp = fma(G[r], d_row[r], hp);
-      h_col = grp_allsum(hp);
-#pragma unroll
-      for (int b = 0; b < UD; b++) hu[b] = readlane_d(h_col, XP + b);
-    }
 
     if (!DEEP && !MAIN) late_pf();
     if (!MAIN && cons) {
@@ -507,19 +488,10 @@ __global__ void __launch_bounds__(64, MODE == 2 ? 2 : (MODE == 1 ? PMPC_AS_DEEP_
     Pipe A, B;
     fetch_early(jtop, A);
     fetch_late(jtop, jtop >= 1 ? jtop - 1 : 0, A);
-#if PMPC_AS_PINGPONG
-    for (; j - 1 >= jmin; j -= 2) {
-      stage(std::true_type{}, j, A, B);
-      __builtin_amdgcn_sched_barrier(0);  // (no instruction motion across stages: the scheduler would overlap them and spill)
-      stage(std::true_type{}, j - 1, B, A);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#else
     for (; j >= jmin; j--) {
       stage(std::true_type{}, j, A, B);
       A = B;
     }
-#endif
     if (j >= jmin) {
       stage(std::true_type{}, j, A, B);
       A = B;
@@ -538,7 +510,7 @@ __global__ void __launch_bounds__(64, MODE == 2 ? 2 : (MODE == 1 ? PMPC_AS_DEEP_
 // base point = base + clamped step (absolute), statuses, feed-forward of a settled particle's next round, counters
 // ------------------------------------------------------------------------------------------------
 // Loop structure as in k_bwd_as: the consensus stages and stage 0 go through the general body, the free stages j >= 1 through
-// a branch-free MAIN body, two per loop trip with the prefetch register sets swapping roles.
+// a branch-free MAIN body, one per loop trip (A = B); PF2: three per trip, the ring's roles static.
 // PF2: data requested two stages ahead (ring of three register sets; the default); else one stage ahead (two sets).  Both fit
 // 4 waves per SIMD.
 // Memory instructions per stage (the sweep is bound by their count, not by bytes — DESIGN.md section 6): the per-control
@@ -1055,140 +1027,50 @@ __global__ void __launch_bounds__(1024) k_as_perm(const int *settled, int M, int
   as_perm_block(settled, M, perm);
 }
 
-// CONE instantiations of the two sweeps: every compiled (xdim, udim) pair with udim >= 2 (ten more kernels each)
-template <int XD, int UD>
-constexpr bool cone_dims() { return UD >= 2; }
-// (xdim, udim) pairs with fp32-storage instantiations (class MT = float) of the two sweeps
-template <int XD, int UD>
-constexpr bool f32_dims() { return (XD == 12 && UD == 4) || (XD == 6 && UD == 3) || (XD == 4 && UD == 2); }
-// XBOX instantiations of the factor sweep: every compiled (xdim, udim) pair (five more kernels each)
-template <int XD, int UD>
-constexpr bool xbox_dims() { return true; }
+// Run-time field of a variant record -> template argument: f gets the value as a std::integral_constant.
+template <class F>
+void lift(bool v, F &&f) {
+  if (v) f(std::true_type{}); else f(std::false_type{});
+}
+template <class F>
+void lift3(int v, F &&f) {
+  if (v == 0) f(std::integral_constant<int, 0>{}); else if (v == 1) f(std::integral_constant<int, 1>{}); else f(std::integral_constant<int, 2>{});
+}
+[[noreturn]] void no_such_variant(const char *sweep, int x, int u) {  // (cannot happen: tests/test_as_variant.py walks the selectors against the predicates)
+  fprintf(stderr, "pmpc_hip: %s: the selected variant is not compiled for xdim %d, udim %d (as_variant.h)\n", sweep, x, u);
+  throw PmpcHipError{-1, sweep, __FILE__, __LINE__};
+}
+const AsSweepKnobs &as_sweep_knobs() {  // read once per process
+  static const AsSweepKnobs k = {getenv("PMPC_AS_DEEP2_MAXM") ? atoi(getenv("PMPC_AS_DEEP2_MAXM")) : PMPC_AS_DEEP2_MAXM,
+                                 getenv("PMPC_AS_DEEP_MAXM") ? atoi(getenv("PMPC_AS_DEEP_MAXM")) : PMPC_AS_DEEP_WAVES * 1024,
+                                 getenv("PMPC_AS_FWD_PF2_MAXM") ? atoi(getenv("PMPC_AS_FWD_PF2_MAXM")) : (1 << 30)};
+  return k;
+}
+
+// The selected variant's fields become template arguments; only what as_variant.h lists as compiled is instantiated.
 template <int XD, int UD>
 void launch_bwd_as_t(const LQArgs &a, hipStream_t s) {
-  // waves per SIMD this launch brings (1024 SIMDs): <= 2 deep2, <= 3 deep, else lean (see k_bwd_as)
-  static const int m2 = getenv("PMPC_AS_DEEP2_MAXM") ? atoi(getenv("PMPC_AS_DEEP2_MAXM")) : PMPC_AS_DEEP2_MAXM;
-  static const int m1 = getenv("PMPC_AS_DEEP_MAXM") ? atoi(getenv("PMPC_AS_DEEP_MAXM")) : PMPC_AS_DEEP_WAVES * 1024;
-  int mode = a.M <= m2 ? 2 : (a.M <= m1 ? 1 : 0);
-  // the DEFECT instantiation of the deep variant needs 127 registers (4 waves per SIMD without help): never the lean one
-  if (a.defect && mode == 0) mode = 1;
- const dim3 grd(a.M), blk(64);
-  if (a.mat32) {  // fp32-storage mode: the deep variants, with or without stage cones
-    if constexpr (f32_dims<XD, UD>()) {
-      if (mode == 0) mode = 1;
-#define PMPC_BWD32(MD, SK, DF, CN) hipLaunchKernelGGL((k_bwd_as<XD, UD, MD, SK, DF, CN, float>), grd, blk, 0, s, a)
-#define PMPC_BWD32_C(MD, SK, DF) do { if (a.cone_H) PMPC_BWD32(MD, SK, DF, true); else PMPC_BWD32(MD, SK, DF, false); } while (0)
-      if (a.defect) { if (mode == 2) PMPC_BWD32_C(2, false, true); else PMPC_BWD32_C(1, false, true); }
-      else if (a.as_settled_in) PMPC_BWD32_C(2, true, false);
-      else { if (mode == 2) PMPC_BWD32_C(2, false, false); else PMPC_BWD32_C(1, false, false); }
-#undef PMPC_BWD32_C
-#undef PMPC_BWD32
-      return;
-    } else {
-      abort();  // (solver.hip asks f32_as_dims_supported first)
+  const BwdAsVariant v = select_bwd_as(a.M, a.defect, a.as_settled_in, a.mat32, a.cone_H, a.xb_D, as_sweep_knobs());
+  bool launched = false;
+  lift3(v.mode, [&](auto MODE) { lift(v.skip, [&](auto SKIP) { lift(v.defect, [&](auto DEFECT) { lift3(v.ex, [&](auto EX) { lift(v.f32, [&](auto F32) {
+    if constexpr (bwd_as_compiled(BwdAsVariant{MODE, SKIP, DEFECT, EX, F32}, XD, UD)) {
+      hipLaunchKernelGGL((k_bwd_as<XD, UD, MODE, SKIP, DEFECT, EX, std::conditional_t<F32, float, double>>), dim3(a.M), dim3(64), 0, s, a);
+      launched = true;
     }
-  }
-  if (a.cone_H) {  // stage cones: the deep variants only (one more register per prefetch set)
-    if constexpr (cone_dims<XD, UD>()) {
-      if (mode == 0) mode = 1;
-      if (a.defect) {
-        if (mode == 2) hipLaunchKernelGGL((k_bwd_as<XD, UD, 2, false, true, true>), grd, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_bwd_as<XD, UD, 1, false, true, true>), grd, blk, 0, s, a);
-      } else if (a.as_settled_in) {
-        hipLaunchKernelGGL((k_bwd_as<XD, UD, 2, true, false, true>), grd, blk, 0, s, a);
-      } else {
-        if (mode == 2) hipLaunchKernelGGL((k_bwd_as<XD, UD, 2, false, false, true>), grd, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_bwd_as<XD, UD, 1, false, false, true>), grd, blk, 0, s, a);
-      }
-      return;
-    } else {
-      abort();  // (solver.hip asks cone_as_dims_supported first)
-    }
-  }
-  if (a.xb_D) {  // state boxes: the deep variants only
-    if constexpr (xbox_dims<XD, UD>()) {
-      if (mode == 0) mode = 1;
-      if (a.defect) {
-        if (mode == 2) hipLaunchKernelGGL((k_bwd_as<XD, UD, 2, false, true, 2>), grd, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_bwd_as<XD, UD, 1, false, true, 2>), grd, blk, 0, s, a);
-      } else if (a.as_settled_in) {
-        hipLaunchKernelGGL((k_bwd_as<XD, UD, 2, true, false, 2>), grd, blk, 0, s, a);
-      } else {
-        if (mode == 2) hipLaunchKernelGGL((k_bwd_as<XD, UD, 2, false, false, 2>), grd, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_bwd_as<XD, UD, 1, false, false, 2>), grd, blk, 0, s, a);
-      }
-      return;
-    } else {
-      abort();  // (solver.hip asks xbox_as_dims_supported first)
-    }
-  }
-#define PMPC_BWD_AS(SK, DF)                                                                      \
-  do {                                                                                           \
-    if (mode == 2) hipLaunchKernelGGL((k_bwd_as<XD, UD, 2, SK, DF>), grd, blk, 0, s, a);         \
-    else if (mode == 1) hipLaunchKernelGGL((k_bwd_as<XD, UD, 1, SK, DF>), grd, blk, 0, s, a);    \
-    else hipLaunchKernelGGL((k_bwd_as<XD, UD, 0, SK, DF>), grd, blk, 0, s, a);                   \
-  } while (0)
-  if (a.defect) PMPC_BWD_AS(false, true);
-  else if (a.as_settled_in) {  // few particles left: the latency regime at every M
-    if (m2 > 0) hipLaunchKernelGGL((k_bwd_as<XD, UD, 2, true, false>), grd, blk, 0, s, a);
-    else hipLaunchKernelGGL((k_bwd_as<XD, UD, 1, true, false>), grd, blk, 0, s, a);
-  }
-  else PMPC_BWD_AS(false, false);
-#undef PMPC_BWD_AS
+  }); }); }); }); });
+  if (!launched) no_such_variant("factor sweep of an active-set round", XD, UD);
 }
 template <int XD, int UD>
 void launch_fwd_as_t(const LQArgs &a, hipStream_t s) {
-  // (two-stage prefetch everywhere since the merged loads freed the registers for 4 waves per SIMD: +0.8 % at 4096 particles;
-  //  PMPC_AS_FWD_PF2_MAXM=<M> puts larger launches back on the one-stage variant)
-  static const int m2 = getenv("PMPC_AS_FWD_PF2_MAXM") ? atoi(getenv("PMPC_AS_FWD_PF2_MAXM")) : (1 << 30);
-  const dim3 grd(a.M), blk(64);
-  if (a.mat32) {
-    if constexpr (f32_dims<XD, UD>()) {
-      if (a.as_uraw && a.as_T && a.Nc == 1) {
-        if (a.defect) hipLaunchKernelGGL((k_fwd_as<XD, UD, true, false, true, float, true>), grd, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_fwd_as<XD, UD, false, true, true, float, true>), grd, blk, 0, s, a);
-      } else if (a.as_uraw) {
-        if (a.defect) hipLaunchKernelGGL((k_fwd_as<XD, UD, true, true, true, float>), grd, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_fwd_as<XD, UD, false, true, true, float>), grd, blk, 0, s, a);
-      } else if (a.as_T && a.Nc == 1) {
-        if (a.defect) hipLaunchKernelGGL((k_fwd_as<XD, UD, true, true, false, float, true>), grd, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_fwd_as<XD, UD, false, true, false, float, true>), grd, blk, 0, s, a);
-      } else {
-        if (a.defect) hipLaunchKernelGGL((k_fwd_as<XD, UD, true, true, false, float>), grd, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_fwd_as<XD, UD, false, true, false, float>), grd, blk, 0, s, a);
-      }
-      return;
-    } else {
-      abort();
+  const FwdAsVariant v = select_fwd_as(a.M, a.Nc, a.defect, a.mat32, a.as_uraw, a.as_T, as_sweep_knobs());
+  bool launched = false;
+  lift(v.defect, [&](auto DEFECT) { lift(v.pf2, [&](auto PF2) { lift(v.cone, [&](auto CONE) { lift(v.f32, [&](auto F32) { lift(v.sens, [&](auto SENS) {
+    if constexpr (fwd_as_compiled(FwdAsVariant{DEFECT, PF2, CONE, F32, SENS}, XD, UD)) {
+      hipLaunchKernelGGL((k_fwd_as<XD, UD, DEFECT, PF2, CONE, std::conditional_t<F32, float, double>, SENS>), dim3(a.M), dim3(64), 0, s, a);
+      launched = true;
     }
-  }
-  if (a.as_uraw) {
-    if constexpr (cone_dims<XD, UD>()) {
-      if (a.as_T && a.Nc == 1) {  // sensitivity records + elementwise update of the settled particles, with stage cones
-        if (a.defect) hipLaunchKernelGGL((k_fwd_as<XD, UD, true, false, true, double, true>), grd, blk, 0, s, a);  // (one-stage ring: registers)
-        else hipLaunchKernelGGL((k_fwd_as<XD, UD, false, true, true, double, true>), grd, blk, 0, s, a);
-        return;
-      }
-      if (a.defect) hipLaunchKernelGGL((k_fwd_as<XD, UD, true, true, true>), grd, blk, 0, s, a);
-      else hipLaunchKernelGGL((k_fwd_as<XD, UD, false, true, true>), grd, blk, 0, s, a);
-      return;
-    } else {
-      abort();
-    }
-  }
-  if (a.as_T && a.Nc == 1) {  // sensitivity records + elementwise update of the settled particles (solver.hip decides when)
-    // (x12 u4, DEFECT: 128 registers + 2 spilled dwords outside the stage loop; the one-stage ring, 93 registers, measured 1 - 2 % slower)
-    if (a.defect) hipLaunchKernelGGL((k_fwd_as<XD, UD, true, true, false, double, true>), grd, blk, 0, s, a);
-    else hipLaunchKernelGGL((k_fwd_as<XD, UD, false, true, false, double, true>), grd, blk, 0, s, a);
-    return;
-  }
-  if (a.M <= m2) {
-    if (a.defect) hipLaunchKernelGGL((k_fwd_as<XD, UD, true, true>), grd, blk, 0, s, a);
-    else hipLaunchKernelGGL((k_fwd_as<XD, UD, false, true>), grd, blk, 0, s, a);
-  } else {
-    if (a.defect) hipLaunchKernelGGL((k_fwd_as<XD, UD, true, false>), grd, blk, 0, s, a);
-    else hipLaunchKernelGGL((k_fwd_as<XD, UD, false, false>), grd, blk, 0, s, a);
-  }
+  }); }); }); }); });
+  if (!launched) no_such_variant("forward sweep of an active-set round", XD, UD);
 }
 
 }  // namespace
@@ -1198,35 +1080,41 @@ extern "C" int pmpc_debug_timeline_read(unsigned long long *out) {  // 3 x 128 x
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pmpc_tl), sizeof(unsigned long long) * 3 * 128 * PMPC_TL_STAMPS);
 }
 #endif
-bool f32_as_dims_supported(int x, int u) {
-#define X(xd, ud) if (x == xd && u == ud) return f32_dims<xd, ud>();
+static bool as_dims_compiled(int x, int u) {
+#define X(xd, ud) if (x == xd && u == ud) return true;
   PMPC_FAST_DIMS(X)
 #undef X
   return false;
 }
-bool xbox_as_dims_supported(int x, int u) {
-#define X(xd, ud) if (x == xd && u == ud) return xbox_dims<xd, ud>();
-  PMPC_FAST_DIMS(X)
-#undef X
-  return false;
-}
-bool cone_as_dims_supported(int x, int u) {
-#define X(xd, ud) if (x == xd && u == ud) return cone_dims<xd, ud>();
-  PMPC_FAST_DIMS(X)
-#undef X
-  return false;
+bool f32_as_dims_supported(int x, int u) { return as_dims_compiled(x, u) && as_f32_dims(x, u); }
+bool xbox_as_dims_supported(int x, int u) { return as_dims_compiled(x, u) && as_xbox_dims(x, u); }
+bool cone_as_dims_supported(int x, int u) { return as_dims_compiled(x, u) && as_cone_dims(x, u); }
+// Host-only view of the selection (include/pmpc_abi.h; tests/test_as_variant.py): no device needed.
+int pmpc_as_sweep_variant(int sweep, int xdim, int udim, int M, int Nc, unsigned flags, const int *knobs, int *out) {
+  if ((sweep != 0 && sweep != 1) || !as_dims_compiled(xdim, udim) || !out) return -1;
+  const AsSweepKnobs k = knobs ? AsSweepKnobs{knobs[0], knobs[1], knobs[2]} : AsSweepKnobs{PMPC_AS_DEEP2_MAXM, PMPC_AS_DEEP_WAVES * 1024, 1 << 30};
+  const bool defect = flags & 1, settled_in = flags & 2, mat32 = flags & 4, cone_H = flags & 8, xb_D = flags & 16, as_uraw = flags & 32, as_T = flags & 64;
+  out[5] = f32_as_dims_supported(xdim, udim); out[6] = cone_as_dims_supported(xdim, udim); out[7] = xbox_as_dims_supported(xdim, udim);
+  if (sweep == 0) {
+    const BwdAsVariant v = select_bwd_as(M, defect, settled_in, mat32, cone_H, xb_D, k);
+    out[0] = v.mode; out[1] = v.skip; out[2] = v.defect; out[3] = v.ex; out[4] = v.f32;
+    return bwd_as_compiled(v, xdim, udim);
+  }
+  const FwdAsVariant v = select_fwd_as(M, Nc, defect, mat32, as_uraw, as_T, k);
+  out[0] = v.defect; out[1] = v.pf2; out[2] = v.cone; out[3] = v.f32; out[4] = v.sens;
+  return fwd_as_compiled(v, xdim, udim);
 }
 void launch_bwd_as(const LQArgs &a, hipStream_t s) {
 #define X(xd, ud) if (a.x == xd && a.u == ud) { launch_bwd_as_t<xd, ud>(a, s); return; }
   PMPC_FAST_DIMS(X)
 #undef X
-  abort();
+  no_such_variant("factor sweep of an active-set round", a.x, a.u);
 }
 void launch_fwd_as(const LQArgs &a, hipStream_t s) {
 #define X(xd, ud) if (a.x == xd && a.u == ud) { launch_fwd_as_t<xd, ud>(a, s); return; }
   PMPC_FAST_DIMS(X)
 #undef X
-  abort();
+  no_such_variant("forward sweep of an active-set round", a.x, a.u);
 }
 void launch_as_ctl(AsCtl *ctl, const int *cnt_part, int M, const int *fail, int reduce, int decide, int last_of_batch, AsCtl *mirror,
                    unsigned long long *mirror_seq, unsigned long long seq, hipStream_t s, double *tail, const double *viol, const int *open_part) {
