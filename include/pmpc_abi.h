@@ -328,6 +328,50 @@ int pmpc_scp_residual_device(pmpc_ctx *ctx, size_t xdim, size_t udim, size_t N, 
 int pmpc_scp_loop_device(pmpc_ctx *ctx, int model, const double *params, const pmpc_problem *p, double *f2, double *fx2, double *fu2,
                          int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out);
 
+/* Linearised nonlinear costs (the reference's `lin_cost_fn`, pmpc/scp_mpc.py:171-185, 352: the callback returns the cost gradients
+ * (cx, cu) at (X_prev, U_prev) and the loop tracks X_ref - Q^-1 cx, U_ref - R^-1 cu for that iteration).
+ *
+ * pmpc_ref_shift_device: out[r] = ref[r] - A[r]^-1 c[r] for `rows` independent blocks — A (rows, dim, dim) symmetric positive definite
+ * blocks in the column-major block layout above (Q with dim = xdim, rows = M N; R with dim = udim), c, ref, out (rows, dim); out may
+ * be ref.  Cholesky and two triangular solves per block, fp64; only the lower triangle (row >= column) of a block is read.  A block
+ * with a pivot that is not positive (or NaN) gets NaN in its row of `out` and counts in pmpc_ref_shift_bad_pivots; the other rows
+ * are not affected.  Asynchronous on pmpc_stream().  Returns 0; 2 and launches nothing if dim is 0 or above 16; 1 on a HIP error.
+ * pmpc_ref_shift_bad_pivots: blocks refused since the context was created or the count was last reset (synchronises the stream). */
+int pmpc_ref_shift_device(pmpc_ctx *ctx, size_t dim, size_t rows, const double *A, const double *c, const double *ref, double *out);
+long long pmpc_ref_shift_bad_pivots(pmpc_ctx *ctx, int reset);
+
+/* A built-in cost for loops that have no Python callable.  kind 1, obstacles: K <= 16 Gaussian bumps shared by all particles,
+ *   J_obs = sum_{i,j} sum_k w_k exp(-|x_ij[pos_idx] - c_jk|^2 / (2 sigma_k^2)),
+ * x_ij = stage j (0-based: the state after j + 1 steps, row j of X_prev) of particle i; pos_idx: pos_dim = 2 or 3 state indices;
+ * centres (device): (K, pos_dim) if per_stage = 0, (N, K, pos_dim) if 1 (moving obstacles); sigma, w (device): (K). */
+typedef struct pmpc_scp_cost {
+  int kind; /* 0 none, 1 obstacles */
+  int K, pos_dim;
+  int pos_idx[3];
+  int per_stage;
+  const double *centres, *sigma, *w;
+} pmpc_scp_cost;
+size_t pmpc_abi_scp_cost_size(void); /* sizeof(pmpc_scp_cost) as the library was built (see pmpc_abi_struct_sizes) */
+
+/* cx (device, (xdim, N, M), dense: zero outside pos_idx) = gradient of J_obs at X_prev.  Returns 0; 2 and launches nothing for a cost
+ * that is not a valid kind-1 description for this xdim (K, pos_dim, pos_idx out of range, xdim above 16, a null pointer). */
+int pmpc_obstacle_cost_grad_device(pmpc_ctx *ctx, const pmpc_scp_cost *cost, size_t xdim, size_t N, size_t M, const double *X_prev,
+                                   double *cx);
+/* The two in one launch, cx never stored: out = X_ref - Q^-1 cx(X_prev) (out may be X_ref); what pmpc_scp_loop_device_cost enqueues. */
+int pmpc_obstacle_ref_shift_device(pmpc_ctx *ctx, const pmpc_scp_cost *cost, size_t xdim, size_t N, size_t M, const double *X_prev,
+                                   const double *Q, const double *X_ref, double *out);
+
+/* pmpc_scp_loop_device with a built-in cost (`cost` NULL or kind 0: exactly pmpc_scp_loop_device, launch for launch).  Every
+ * iteration's sub-problem tracks X_ref - Q^-1 cx(X_prev) instead of p->X_ref; the shifted reference lives in the context's
+ * workspace, two sets of (xdim, N, M) used like the linearisation scratch sets: each linearisation launch — the speculative one
+ * behind a sub-problem's rounds included — is followed by the shift into the set that goes with it, so a solve that continues never
+ * sees its reference change.  p->X_ref is not written.  Q must hold symmetric positive definite blocks (a block that is not makes
+ * its reference NaN, and the sub-problem fails).  Refused before anything runs (0, infos[0].status = 2, as for an unknown model
+ * id): an invalid cost description, and a cost together with PMPC_F32_MATRICES (the shift reads Q as doubles). */
+int pmpc_scp_loop_device_cost(pmpc_ctx *ctx, int model, const double *params, const pmpc_problem *p, double *f2, double *fx2,
+                              double *fu2, int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out,
+                              const pmpc_scp_cost *cost);
+
 /* Live kernel timing for bench.py: HIP events on pmpc_stream() around the launches of a class
  * (0 backward+factor, 1 backward vector-only, 2 forward, 3 consensus reduce+solve).
  * level 0 = off, 1 = class 0 only (the dominant kernel; what bench.py's roofline needs), 2 = every class
@@ -338,7 +382,7 @@ void pmpc_profile_read(pmpc_ctx *ctx, double *ms4, long long *n4);
  * never enter class 0, whose launches all process every (particle, stage): totals as of the last pmpc_profile_read. */
 void pmpc_profile_read_partial(pmpc_ctx *ctx, double *ms, long long *n);
 /* every launch class as of the last pmpc_profile_read: 0 full factor sweep, 1 vector sweep, 2 forward sweep, 3 consensus
- * reduce + solve, 4 factor sweeps that skip settled particles, 5 active-set bookkeeping, 6 linearisation, 7 SCP residual */
+ * reduce + solve, 4 factor sweeps that skip settled particles, 5 active-set bookkeeping, 6 linearisation (and the reference shift of a built-in cost), 7 SCP residual */
 void pmpc_profile_read_all(pmpc_ctx *ctx, double *ms, long long *launches, int count);
 
 /* Checkpointed restart of the later rounds' factor sweeps (option as_ckpt), counted since the last reset: out4 = {sweeps that

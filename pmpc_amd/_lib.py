@@ -28,6 +28,8 @@ ABI_SYMBOLS = [
     "pmpc_set_option", "pmpc_get_option", "pmpc_abi_struct_sizes", "pmpc_lcone_solve_host_ex", "pmpc_restart_stats",
     "pmpc_linearize_compact_device", "pmpc_expand_jac_device", "pmpc_jac_compact_doubles", "pmpc_jac_live_mask",
     "pmpc_as_sweep_variant",
+    "pmpc_ref_shift_device", "pmpc_ref_shift_bad_pivots", "pmpc_obstacle_cost_grad_device", "pmpc_obstacle_ref_shift_device",
+    "pmpc_scp_loop_device_cost", "pmpc_abi_scp_cost_size",
 ]
 
 
@@ -48,6 +50,12 @@ class PmpcInfo(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int), ("ipm_iters", ctypes.c_int), ("structured_solves", ctypes.c_int),
                 ("fast_path", ctypes.c_int), ("mu", ctypes.c_double), ("slack_res", ctypes.c_double),
                 ("max_violation", ctypes.c_double), ("outer_solves", ctypes.c_int), ("active_set_rounds", ctypes.c_int)]
+
+
+class PmpcScpCost(ctypes.Structure):
+    """pmpc_scp_cost (include/pmpc_abi.h): the built-in cost of pmpc_scp_loop_device_cost."""
+    _fields_ = [("kind", ctypes.c_int), ("K", ctypes.c_int), ("pos_dim", ctypes.c_int), ("pos_idx", ctypes.c_int * 3), ("per_stage", ctypes.c_int),
+                ("centres", ctypes.c_void_p), ("sigma", ctypes.c_void_p), ("w", ctypes.c_void_p)]
 
 
 def load():
@@ -132,6 +140,22 @@ def load():
     lib.pmpc_scp_loop_device.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(PmpcProblem), vp, vp, vp, ctypes.c_int, ctypes.c_int, vp,
                                          ctypes.POINTER(PmpcInfo), ctypes.POINTER(ctypes.c_int)]
     lib.pmpc_scp_loop_device.restype = ctypes.c_int
+    if hasattr(lib, "pmpc_scp_loop_device_cost"):  # (likewise: an A/B library of an older source has no cost entry points)
+        lib.pmpc_ref_shift_device.argtypes = [vp, sz, sz, vp, vp, vp, vp]
+        lib.pmpc_ref_shift_device.restype = ctypes.c_int
+        lib.pmpc_ref_shift_bad_pivots.argtypes = [vp, ctypes.c_int]
+        lib.pmpc_ref_shift_bad_pivots.restype = ctypes.c_longlong
+        lib.pmpc_obstacle_cost_grad_device.argtypes = [vp, ctypes.POINTER(PmpcScpCost), sz, sz, sz, vp, vp]
+        lib.pmpc_obstacle_cost_grad_device.restype = ctypes.c_int
+        lib.pmpc_obstacle_ref_shift_device.argtypes = [vp, ctypes.POINTER(PmpcScpCost), sz, sz, sz, vp, vp, vp, vp]
+        lib.pmpc_obstacle_ref_shift_device.restype = ctypes.c_int
+        lib.pmpc_scp_loop_device_cost.argtypes = lib.pmpc_scp_loop_device.argtypes + [ctypes.POINTER(PmpcScpCost)]
+        lib.pmpc_scp_loop_device_cost.restype = ctypes.c_int
+        lib.pmpc_abi_scp_cost_size.argtypes = []
+        lib.pmpc_abi_scp_cost_size.restype = sz
+        if lib.pmpc_abi_scp_cost_size() != ctypes.sizeof(PmpcScpCost):
+            raise ImportError(f"{LIB_PATH} and pmpc_amd/_lib.py disagree on pmpc_scp_cost: library {lib.pmpc_abi_scp_cost_size()} bytes, "
+                              f"binding {ctypes.sizeof(PmpcScpCost)}: rebuild the library")
     lib.pmpc_version.argtypes = []
     lib.pmpc_version.restype = ctypes.c_char_p
     # layout check: the library's structs against this binding's mirrors (include/pmpc_abi.h: pmpc_abi_struct_sizes)

@@ -12,6 +12,7 @@
 #include <dlfcn.h>
 
 #include "solver_internal.h"
+#include "cost_lin.h"
 
 namespace {
 
@@ -307,6 +308,7 @@ extern "C" {
 const char *pmpc_version(void) { return "pmpc_hip 0.4 (gfx950)"; }
 // layout check of the two structs the bindings mirror (a stale library under a newer binding, or the reverse, must fail loudly)
 void pmpc_abi_struct_sizes(size_t *problem, size_t *info) { *problem = sizeof(pmpc_problem); *info = sizeof(pmpc_info); }
+size_t pmpc_abi_scp_cost_size(void) { return sizeof(pmpc_scp_cost); }
 
 int pmpc_create(pmpc_ctx **out, int device) {
   int ndev = 0;
@@ -372,7 +374,7 @@ void pmpc_destroy(pmpc_ctx *c) {
                    &w.warm_lux, &w.Hadd, &w.wu_soc, &w.soc_zl, &w.soc_zu, &w.soc_zc, &w.soc_dzl, &w.soc_dzu, &w.soc_dzc, &w.soc_sl, &w.soc_su, &w.soc_sc, &w.soc_dsl,
                    &w.soc_dsu, &w.soc_dsc, &w.soc_cl, &w.soc_cu, &w.soc_cc, &w.soc_wU, &w.soc_wzl, &w.soc_wzu, &w.soc_wzc, &w.as_act, &w.as_cnt, &w.as_cntp, &w.as_settled, &w.cons_lo, &w.cons_hi, &w.as_ctl, &w.as_delta, &w.as_viol, &w.as_ck, &w.as_jhi, &w.ck_stat, &w.Hc_grp, &w.as_T, &w.xb_qmax, &w.as_perm,
                    &w.sa_f, &w.sa_fx, &w.sa_fu, &w.sa_Xp, &w.sa_Up, &w.sa_Q, &w.sa_R, &w.sa_Xr, &w.sa_Ur, &w.sa_lo, &w.sa_hi, &w.sa_Xo, &w.sa_Uo,
-                   &w.sa_cl, &w.sa_ch, &w.cone_A, &w.cone_c, &w.cone_z, &w.cone_rec, &w.cone_uraw, &w.as_open, &w.xb_z, &w.xb_st, &w.xb_D, &w.xb_g, &w.m64[0], &w.m64[1], &w.m64[2], &w.m64[3]};
+                   &w.sa_cl, &w.sa_ch, &w.cone_A, &w.cone_c, &w.cone_z, &w.cone_rec, &w.cone_uraw, &w.as_open, &w.xb_z, &w.xb_st, &w.xb_D, &w.xb_g, &w.m64[0], &w.m64[1], &w.m64[2], &w.m64[3], &w.cost_ref[0], &w.cost_ref[1], &w.cost_bad};
   for (DevBuf *b : all) b->release();
   for (SlabBufs *sb : {&w.sx, &w.su})
     for (DevBuf *b : {&sb->lo, &sb->hi, &sb->tl, &sb->tu, &sb->ll, &sb->lu, &sb->cl, &sb->cu, &sb->D, &sb->w}) b->release();
@@ -523,6 +525,58 @@ int pmpc_linearize_device(pmpc_ctx *c, int model, size_t N, size_t M, const doub
     HIP_CHECK(hipGetLastError());
   } catch (const PmpcHipError &) {
     return 2;
+  }
+  return 0;
+}
+
+// Linearised nonlinear costs (cost_lin.hip).  The counter of refused blocks lives in the workspace, zeroed when it is created.
+static unsigned *cost_bad_counter(pmpc_ctx *c) {
+  if (c->ws.cost_bad.ensure(sizeof(unsigned))) HIP_CHECK(hipMemsetAsync(c->ws.cost_bad.p, 0, sizeof(unsigned), c->stream));
+  return (unsigned *)c->ws.cost_bad.p;
+}
+int pmpc_ref_shift_device(pmpc_ctx *c, size_t dim, size_t rows, const double *A, const double *cv, const double *ref, double *out) {
+  if (dim < 1 || dim > (size_t)REF_SHIFT_MAX_DIM) return 2;
+  try {
+    HIP_CHECK(hipSetDevice(c->device));
+    ProfScope ps(c, 6);
+    launch_ref_shift((int)dim, (long long)rows, A, cv, ref, out, cost_bad_counter(c), c->stream);
+    HIP_CHECK(hipGetLastError());
+  } catch (const PmpcHipError &) {
+    return 1;
+  }
+  return 0;
+}
+long long pmpc_ref_shift_bad_pivots(pmpc_ctx *c, int reset) {
+  if (!c || !c->ws.cost_bad.p) return 0;
+  unsigned n = 0;
+  (void)hipSetDevice(c->device);
+  HIP_WARN(hipStreamSynchronize(c->stream));
+  HIP_WARN(hipMemcpy(&n, c->ws.cost_bad.p, sizeof(n), hipMemcpyDeviceToHost));
+  if (reset) HIP_WARN(hipMemset(c->ws.cost_bad.p, 0, sizeof(n)));
+  return (long long)n;
+}
+int pmpc_obstacle_cost_grad_device(pmpc_ctx *c, const pmpc_scp_cost *cost, size_t xdim, size_t N, size_t M, const double *X_prev, double *cx) {
+  if (!obstacle_cost_valid(cost, (int)xdim)) return 2;
+  try {
+    HIP_CHECK(hipSetDevice(c->device));
+    ProfScope ps(c, 6);
+    launch_obstacle_grad(*cost, (int)xdim, (int)N, (int)M, X_prev, cx, c->stream);
+    HIP_CHECK(hipGetLastError());
+  } catch (const PmpcHipError &) {
+    return 1;
+  }
+  return 0;
+}
+int pmpc_obstacle_ref_shift_device(pmpc_ctx *c, const pmpc_scp_cost *cost, size_t xdim, size_t N, size_t M, const double *X_prev, const double *Q,
+                                   const double *X_ref, double *out) {
+  if (!obstacle_cost_valid(cost, (int)xdim)) return 2;
+  try {
+    HIP_CHECK(hipSetDevice(c->device));
+    ProfScope ps(c, 6);
+    launch_obstacle_ref_shift(*cost, (int)xdim, (int)N, (int)M, X_prev, Q, X_ref, out, cost_bad_counter(c), c->stream);
+    HIP_CHECK(hipGetLastError());
+  } catch (const PmpcHipError &) {
+    return 1;
   }
   return 0;
 }
@@ -710,7 +764,20 @@ int solve_slew_increment_form(pmpc_ctx *c, const pmpc_problem *p, pmpc_info *inf
 // -------------------------------------------------------------------------------------------------
 int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmpc_problem *p0, double *f2, double *fx2, double *fu2,
                          int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out) {
+  return pmpc_scp_loop_device_cost(c, model, params, p0, f2, fx2, fu2, steps, first_cold, res, infos, last_in_out, nullptr);
+}
+int pmpc_scp_loop_device_cost(pmpc_ctx *c, int model, const double *params, const pmpc_problem *p0, double *f2, double *fx2, double *fu2,
+                              int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out, const pmpc_scp_cost *cost) {
   pmpc_problem p = *p0;
+  // Built-in cost: the sub-problem of an iteration tracks X_ref - Q^-1 cx(X_prev).  The shifted reference has two sets in the
+  // workspace, indexed like F below; shift(set, X) goes behind every linearisation launch, into the set that launch writes.
+  const bool with_cost = cost != nullptr && cost->kind != 0;
+  double *Xr[2] = {nullptr, nullptr};
+  unsigned *cost_bad = nullptr;
+  auto shift = [&](int set, const double *X) {  // (inside the linearisation's ProfScope: timed in class 6 with it)
+    if (!with_cost) return;
+    launch_obstacle_ref_shift(*cost, (int)p0->xdim, (int)p0->N, (int)p0->M, X, p0->Q, p0->X_ref, Xr[set], cost_bad, c->stream);
+  };
   // trajectory buffers A = (X_prev, U_prev), B = (X_out, U_out); linearisation buffers 0 = (f, fx, fu), 1 = (f2, fx2, fu2)
   double *XA = const_cast<double *>(p0->X_prev), *UA = const_cast<double *>(p0->U_prev), *XB = p0->X_out, *UB = p0->U_out;
   double *F[2][3] = {{const_cast<double *>(p0->f), const_cast<double *>(p0->fx), const_cast<double *>(p0->fu)}, {f2, fx2, fu2}};
@@ -729,7 +796,8 @@ int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmp
                           c->opt[OPT_AS_WARM] != 0.0 && c->opt[OPT_POLISH_MU] > 0.0;
   bool compact_set[2] = {false, false};  // what the linearisation buffer sets hold
   int done = 0, cur = 0;
-  if (!model_known(model)) {  // nothing runs (the kernels of some other model would read the caller's arrays with ITS dimensions)
+  // (likewise refused: a cost description the kernels cannot run, and a cost next to fp32-stored matrices — the shift reads Q as doubles)
+  if (!model_known(model) || (with_cost && (jac32 || !obstacle_cost_valid(cost, (int)p0->xdim)))) {  // nothing runs (the kernels of some other model would read the caller's arrays with ITS dimensions)
     if (infos && steps > 0) { memset(&infos[0], 0, sizeof(pmpc_info)); infos[0].status = 2; }
     if (last_in_out) *last_in_out = 0;
     return 0;
@@ -738,6 +806,11 @@ int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmp
   try {
     HIP_CHECK(hipSetDevice(c->device));
     HIP_CHECK(hipMemsetAsync(res, 0, (size_t)steps * sizeof(double), c->stream));  // (the residual kernel takes a maximum into its slot)
+    if (with_cost) {
+      for (DevBuf &b : c->ws.cost_ref) b.ensure((size_t)p0->M * p0->N * p0->xdim * sizeof(double));
+      Xr[0] = c->ws.cost_ref[0].d(); Xr[1] = c->ws.cost_ref[1].d();
+      cost_bad = cost_bad_counter(c);
+    }
     for (; done < steps; done++) {
       double *Xp = (done & 1) ? XB : XA, *Up = (done & 1) ? UB : UA, *Xo = (done & 1) ? XA : XB, *Uo = (done & 1) ? UA : UB;
       if (!lin_ready) {
@@ -747,8 +820,10 @@ int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmp
           launch_linearize_compact(model, (int)p.N, (int)p.M, p.x0, Xp, Up, params, F[cur][0], F[cur][1], nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream);
         else
           launch_linearize(model, (int)p.N, (int)p.M, p.x0, Xp, Up, params, F[cur][0], F[cur][1], F[cur][2], c->stream, jac32);
+        shift(cur, Xp);
       }
       p.f = F[cur][0]; p.fx = F[cur][1]; p.fu = F[cur][2];
+      if (with_cost) p.X_ref = Xr[cur];
       c->jac_compact_fx = compact_set[cur] ? F[cur][1] : nullptr;
       c->jac_compact_model = model;
       p.X_prev = Xp; p.U_prev = Up; p.X_out = Xo; p.U_out = Uo;
@@ -767,6 +842,7 @@ int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmp
           else
             launch_linearize_with_residual(model, (int)p.N, (int)p.M, p.x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], Xo, Xp, Uo,
                                            Up, (int)p.xdim, (int)p.udim, res + done, c->stream, jac32);
+          shift(cur ^ 1, Xo);
           res_dirty = true;
           return;
         }
@@ -783,6 +859,7 @@ int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmp
             launch_linearize_compact(model, (int)p.N, (int)p.M, p.x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream);
           else
             launch_linearize(model, (int)p.N, (int)p.M, p.x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], c->stream, jac32);
+          shift(cur ^ 1, Xo);
         }
       };
       c->spec_fired = c->spec_ok = false;

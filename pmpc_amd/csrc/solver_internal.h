@@ -68,6 +68,8 @@ struct Workspace {
   DevBuf xb_qmax;  // per particle: largest diagonal cost entry (penalty scale of the state rows), found once per attempt
   DevBuf xb_z, xb_st, xb_D, xb_g;  // state boxes inside the active-set rounds (kernels_xbox.hip)
   DevBuf jac_tmp;  // compact Jacobian records copied aside while they are expanded into the caller's fx / fu (QpSolve::densify)
+  DevBuf cost_ref[2];  // pmpc_scp_loop_device_cost: the shifted reference X_ref - Q^-1 cx, one per linearisation scratch set
+  DevBuf cost_bad;  // blocks pmpc_ref_shift_device refused (one unsigned counter; cost_lin.hip)
   DevBuf m64[4];  // fp32-storage mode: fx, fu, Q, R widened for the paths that run the fp64 kernels
   // warm start: the early interior-point iterate (mu <= 0.5) remembered from the previous solve of the same shape
   DevBuf warmU, warm_llu, warm_luu, warm_llx, warm_lux;

@@ -246,6 +246,88 @@ class DeviceSolver:
         assert st == 0, st
         return fx, fu
 
+    # ---- linearised nonlinear costs (csrc/cost_lin.hip) ------------------------------------------------------
+    def _need(self, symbol):
+        if not hasattr(self.lib, symbol):  # (an older library loaded through PMPC_HIP_LIB: _lib.load leaves the cost prototypes out)
+            raise RuntimeError(f"{_lib.LIB_PATH} has no {symbol}: it predates the linearised-cost entry points, rebuild it (make -C pmpc_amd/csrc)")
+
+    def check_bad_pivots(self, what):
+        """Raise ValueError if a reference shift since the last check met a block that is not positive definite (reads and clears the
+        device-side counter; synchronises the solver's stream)."""
+        self._need("pmpc_ref_shift_bad_pivots")
+        n = self.lib.pmpc_ref_shift_bad_pivots(self.h, 1)  # (synchronises the solver's stream; the one read of the call)
+        if n:
+            raise ValueError(f"{what}: {n} cost block(s) are not symmetric positive definite (their rows of the result are NaN)")
+
+    def ref_shift(self, A, c, ref, out=None, wait_current_stream=True, check=True):
+        """out = ref - A^-1 c block by block — the reference shift of a linearised cost (pmpc/scp_mpc.py:171-185): A (..., d, d)
+        symmetric positive definite blocks (Q or R; ABI layout, which is immaterial for symmetric blocks), c, ref (..., d), d <= 16;
+        `out` may be `ref`.  A block that is not positive definite gives NaN in its row and (`check`) a ValueError for the whole call
+        after one read of the device-side counter; `check=False` skips that read (and the synchronisation it costs)."""
+        self._need("pmpc_ref_shift_device")
+        d = A.shape[-1]
+        rows = A.numel() // (d * d) if d else 0
+        if not 1 <= d <= 16:
+            raise ValueError(f"ref_shift: block dimension {d} is outside 1 .. 16")
+        assert A.shape[-2] == d and c.shape == ref.shape and c.shape[-1] == d and c.numel() == rows * d, (A.shape, c.shape, ref.shape)
+        out = torch.empty_like(ref) if out is None else out
+        assert out.shape == ref.shape
+        self._before(wait_current_stream)
+        st = self.lib.pmpc_ref_shift_device(self.h, d, rows, _p(A), _p(c), _p(ref), _p(out))
+        self._after(wait_current_stream)
+        if st != 0:
+            raise RuntimeError(f"pmpc_ref_shift_device failed ({st})")
+        if check:
+            self.check_bad_pivots("ref_shift")
+        return out
+
+    def prepare_cost(self, cost, N, x, device="cuda"):
+        """A handle of a built-in cost for repeated `obstacle_cost_grad` / `scp_loop` calls on (N stages, x states): the descriptor
+        and its device arrays, uploaded once.  Both methods take the handle wherever they take the dict."""
+        return self._scp_cost(cost, N, x, device)
+
+    def _scp_cost(self, cost, N, x, device):
+        """dict(kind="obstacles", pos_idx=, centres=, sigma=, w=) -> pmpc_scp_cost (+ the tensors it points to, to be kept alive);
+        a handle of `prepare_cost` passes through."""
+        self._need("pmpc_scp_loop_device_cost")
+        if isinstance(cost, tuple):
+            return cost
+        from .dynamics import _obstacle_arrays
+
+        class _xp:
+            asarray = staticmethod(lambda a: torch.as_tensor(a, dtype=torch.float64, device=device))
+
+        pos_idx, cen, sigma, w = _obstacle_arrays(cost, N, _xp)
+        if max(pos_idx) >= x or min(pos_idx) < 0:
+            raise ValueError(f"obstacle cost: pos_idx {pos_idx} outside the {x} states")
+        keep = [cen.contiguous(), sigma.contiguous(), w.contiguous()]
+        torch.cuda.current_stream(self.device).synchronize()  # (they were just uploaded on the caller's stream; the kernels read them on the solver's)
+        sc = _lib.PmpcScpCost(kind=1, K=int(sigma.shape[0]), pos_dim=len(pos_idx), pos_idx=(ctypes.c_int * 3)(*pos_idx), per_stage=int(cen.shape[0] != 1),
+                              centres=keep[0].data_ptr(), sigma=keep[1].data_ptr(), w=keep[2].data_ptr())
+        return sc, keep
+
+    def obstacle_cost_grad(self, X_prev, cost, *, Q=None, X_ref=None, out=None, wait_current_stream=True, check=True):
+        """Gradient cx (M, N, x) of the built-in obstacle cost (pmpc_amd.dynamics.obstacle_cost is the specification) at X_prev.
+        With `Q` and `X_ref`: the fused form the loops use — returns X_ref - Q^-1 cx from one launch, cx is never stored."""
+        M, N, x = X_prev.shape
+        sc, keep = self._scp_cost(cost, N, x, X_prev.device)
+        out = torch.empty_like(X_prev) if out is None else out
+        self._before(wait_current_stream)
+        if Q is None:
+            st = self.lib.pmpc_obstacle_cost_grad_device(self.h, ctypes.byref(sc), x, N, M, _p(X_prev), _p(out))
+        else:
+            assert Q.shape == (M, N, x, x) and X_ref.shape == (M, N, x)
+            st = self.lib.pmpc_obstacle_ref_shift_device(self.h, ctypes.byref(sc), x, N, M, _p(X_prev), _p(Q), _p(X_ref), _p(out))
+        self._after(wait_current_stream)
+        if st != 0:
+            raise RuntimeError(f"obstacle cost kernels failed ({st})")
+        if Q is not None and check:
+            self.check_bad_pivots("obstacle_cost_grad")
+        if not wait_current_stream:
+            self.sync()
+        del keep  # (the cost's device arrays: the launch is done, or the caller's stream — where torch reuses their memory — waits for it)
+        return out
+
     def scp_residual(self, X, X_prev, U, U_prev, out=None, wait_current_stream=True):
         """max(max_ij ||X - X_prev||_2, max_ij ||U - U_prev||_2) of pmpc/scp_mpc.py:397-403 as a one-element device tensor
         (one fused pass on the solver's stream; inf if a trajectory holds a NaN)."""
@@ -256,23 +338,35 @@ class DeviceSolver:
         self._after(wait_current_stream)
         return out
 
-    def scp_loop(self, model: int, params, steps: int, *, f2, fx2, fu2, first_cold=True, res=None, wait_current_stream=True, **kw):
+    def scp_loop(self, model: int, params, steps: int, *, f2, fx2, fu2, first_cold=True, res=None, wait_current_stream=True, cost=None, **kw):
         """`steps` SCP iterations (linearise -> sub-problem -> residual -> swap) for a built-in dynamics model in ONE library
         call: the host is out of the loop body (no Python / ctypes work between iterations, the residual and the next
         linearisation are enqueued behind the sub-problem's rounds before their outcome is read back).  `kw` as for
         `lqp_solve` / `lsoc_solve` with `f, fx, fu` (scratch the linearisation writes), `X_prev, U_prev` (start iterate,
         OVERWRITTEN) and `X_out, U_out`; `f2, fx2, fu2`: a second scratch set.  Returns (res, infos, last_in_out, done):
         per-iteration residuals (device tensor), per-iteration info dicts, whether the final iterate is in (X_out, U_out)
-        (else in (X_prev, U_prev)), iterations completed."""
+        (else in (X_prev, U_prev)), iterations completed.  `cost=dict(kind="obstacles", pos_idx=, centres=, sigma=, w=)`: the built-in
+        obstacle cost (`obstacle_cost_grad`) is linearised about every iterate and the sub-problem tracks X_ref - Q^-1 cx (float64 Q
+        with symmetric positive definite blocks; refused with status 2 next to float32 matrices)."""
         prob, X_out, U_out = self._problem(**kw)
         res = torch.empty((steps,), dtype=torch.float64, device=f2.device) if res is None else res
         infos = (_lib.PmpcInfo * steps)()
         last = ctypes.c_int(0)
+        if cost is not None:
+            sc, keep = self._scp_cost(cost, kw["f"].shape[1], kw["f"].shape[2], f2.device)
         self._before(wait_current_stream)
         jd = kw["fx"].dtype
-        done = self.lib.pmpc_scp_loop_device(self.h, int(model), _p(params), ctypes.byref(prob), _p(f2), _p(fx2, jd), _p(fu2, jd), int(steps),
-                                             int(bool(first_cold)), _p(res), infos, ctypes.byref(last))
+        if cost is None:
+            done = self.lib.pmpc_scp_loop_device(self.h, int(model), _p(params), ctypes.byref(prob), _p(f2), _p(fx2, jd), _p(fu2, jd), int(steps),
+                                                 int(bool(first_cold)), _p(res), infos, ctypes.byref(last))
+        else:
+            done = self.lib.pmpc_scp_loop_device_cost(self.h, int(model), _p(params), ctypes.byref(prob), _p(f2), _p(fx2, jd), _p(fu2, jd), int(steps),
+                                                      int(bool(first_cold)), _p(res), infos, ctypes.byref(last), ctypes.byref(sc))
+            self.sync()  # (the cost's device arrays are this call's own: the launches that read them are done before they go)
+            del keep
         self._after(wait_current_stream)
+        if cost is not None:
+            self.check_bad_pivots("scp_loop(cost=...): Q")
         out = [{k: getattr(infos[i], k) for k, _ in _lib.PmpcInfo._fields_} for i in range(min(done + 1, steps))]
         if out:
             self.last_info = out[min(done, steps) - 1] if done > 0 else out[0]

@@ -16,6 +16,9 @@ Jacobians, in the reference's `f_fx_fu_fn(X, U) -> f, fx, fu` contract
   forward Euler; checked against complex-step differentiation of its own `f` in tests/test_bicycle_model.py.
 
 These are the specifications the on-device linearisation kernels (csrc/dynamics.hip) follow.
+
+`obstacle_cost` is the specification of the built-in obstacle cost (csrc/cost_lin.hip), `make_obstacle_lin_cost_fn` wraps it as a
+`lin_cost_fn` of the SCP loops (pmpc/scp_mpc.py:171-185).
 """
 from __future__ import annotations
 
@@ -227,6 +230,66 @@ def quadrotor(x, u, p, dt=QUAD_DT):
     fx = np.eye(12) + dt * A
     fu = dt * B
     return f, fx, fu
+
+
+# -------------------------------------------------------------------------------------------------
+# built-in obstacle cost (include/pmpc_abi.h pmpc_scp_cost; NOT in the reference, whose lin_cost_fn is a user callback)
+# -------------------------------------------------------------------------------------------------
+def _obstacle_arrays(cost, N, xp=np):
+    """(pos_idx list, centres (1 | N, K, pos_dim), sigma (K,), w (K,)) of a cost dict(pos_idx=, centres=, sigma=, w=)."""
+    if cost.get("kind", "obstacles") != "obstacles":
+        raise ValueError(f"unknown built-in cost kind {cost.get('kind')!r}: 'obstacles' is the only one")
+    pos_idx = [int(k) for k in cost["pos_idx"]]
+    centres = xp.asarray(cost["centres"])
+    sigma, w = xp.asarray(cost["sigma"]).reshape(-1), xp.asarray(cost["w"]).reshape(-1)
+    K, pd = sigma.shape[0], len(pos_idx)
+    if pd not in (2, 3) or len(set(pos_idx)) != pd or not 1 <= K <= 16:
+        raise ValueError("obstacle cost: pos_idx holds 2 or 3 distinct state indices, and there are 1 to 16 obstacles")
+    if tuple(centres.shape) not in ((K, pd), (N, K, pd)) or w.shape[0] != K:
+        raise ValueError(f"obstacle cost: centres must be ({K}, {pd}) or ({N}, {K}, {pd}) and w ({K},), got {tuple(centres.shape)}, {tuple(w.shape)}")
+    return pos_idx, centres.reshape((-1, K, pd)), sigma, w
+
+
+def obstacle_cost(X, cost):
+    """J = sum_{i,j,k} w_k exp(-|X[i, j, pos_idx] - c_jk|^2 / (2 sigma_k^2)) and its gradient cx (the shape of X, zero outside pos_idx).
+    X (..., N, x): stage j is row j (the state after j + 1 steps, as X_prev of the SCP loop); cost = dict(pos_idx=(2 or 3 state
+    indices), centres=(K, pos_dim) | (N, K, pos_dim) for moving obstacles, sigma=(K,), w=(K,)), K <= 16 obstacles shared by all particles."""
+    X = np.asarray(X, float)
+    pos_idx, cen, sigma, w = _obstacle_arrays(cost, X.shape[-2])
+    d = X[..., None, pos_idx] - cen  # (..., N, K, pos_dim)
+    is2 = 1.0 / (sigma * sigma)
+    e = w * np.exp(-0.5 * np.sum(d * d, -1) * is2)  # (..., N, K)
+    cx = np.zeros_like(X)
+    cx[..., pos_idx] = np.sum((-e * is2)[..., None] * d, -2)
+    return float(np.sum(e)), cx
+
+
+def obstacle_cost_torch(X, cost):
+    """`obstacle_cost` on torch tensors of any device (`cost` entries: tensors on X's device, or anything `torch.as_tensor` takes)."""
+    import torch
+
+    class _xp:  # the two array functions _obstacle_arrays needs
+        asarray = staticmethod(lambda a: torch.as_tensor(a, dtype=X.dtype, device=X.device))
+
+    pos_idx, cen, sigma, w = _obstacle_arrays(cost, X.shape[-2], _xp)
+    d = X[..., None, pos_idx] - cen
+    is2 = 1.0 / (sigma * sigma)
+    e = w * torch.exp(-0.5 * torch.sum(d * d, -1) * is2)
+    cx = torch.zeros_like(X)
+    cx[..., pos_idx] = torch.sum((-e * is2)[..., None] * d, -2)
+    return torch.sum(e), cx
+
+
+def make_obstacle_lin_cost_fn(cost):
+    """A `lin_cost_fn(X_prev, U_prev, problems) -> (cx, None)` of the obstacle cost for the SCP loops: numpy in, numpy out (the host
+    loop), torch in, torch out (`device=...`)."""
+
+    def lin_cost_fn(X_prev, U_prev, problems=None):
+        if type(X_prev).__module__.split(".")[0] == "torch":
+            return obstacle_cost_torch(X_prev, cost)[1], None
+        return obstacle_cost(X_prev, cost)[1], None
+
+    return lin_cost_fn
 
 
 # -------------------------------------------------------------------------------------------------

@@ -7,14 +7,21 @@ contract, README.md:136-145 / scp_mpc.py:338-342) and returns `f (M,N,x)`, `fx (
 tensors in the usual (row, col) layout — or already in the ABI layout `(M,N,col,row)` with `jacobians_abi_layout=True`,
 which saves one transposing copy of the Jacobian stacks per iteration.  A built-in model (`builtin_model="unicycle" |
 "quadrotor" | "bicycle"`, `params=...`) is linearised by the HIP kernel of csrc/dynamics.hip instead of a Python callable.
-Nothing crosses PCIe inside the loop except the scalars of the `hist` row (one small read per SCP iteration).
+Nothing crosses PCIe inside the loop except the scalars of the `hist` row (one small read per SCP iteration); a built-in cost's
+descriptor is uploaded once before the loop, and the shifts' counter of refused blocks is read once after it.
 
 `solver_settings["extra_cstrs"]` in the reference's tuple format is accepted for that case (pmpc_amd/extra_cstrs.py).
 `soc=dict(W=(q,u), w0=(q,), v=(u,), v0=float, u_interior=(u,))` adds the stage-wise second-order cone
 `||W u + w0|| <= v'u + v0` on every stage's controls (thrust cones; `DeviceSolver.lsoc_solve`).
 
-Host-only features of the reference loop that need the sub-problem on the host (`lin_cost_fn`, `extra_cstrs_fns`,
-filters, `solver_state`) are not offered here; `pmpc_amd.scp_mpc.scp_solve` (the default) has them.
+`lin_cost_fn(X_prev, U_prev, problems)` (pmpc/scp_mpc.py:171-185) receives float64 GPU tensors and returns the cost gradients
+`(cx, cu)`, each a GPU tensor or None; the iteration then tracks `X_ref - Q^-1 cx`, `U_ref - R^-1 cu` (`DeviceSolver.ref_shift`, a HIP
+kernel; `Q` / `R` must be symmetric), while the `obj` column keeps the caller's references, as upstream (:404).
+`builtin_cost=dict(kind="obstacles", pos_idx=..., centres=..., sigma=..., w=...)` is the built-in obstacle cost
+(`pmpc_amd.dynamics.obstacle_cost`), evaluated and applied in one launch.
+
+Host-only features of the reference loop that need the sub-problem on the host (`extra_cstrs_fns`, filters, `solver_state`) are
+not offered here; `pmpc_amd.scp_mpc.scp_solve` (the default) has them.
 """
 from __future__ import annotations
 
@@ -45,10 +52,10 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
                      u0_slew=None, solver_settings: Optional[Dict[str, Any]] = None, device="cuda",
                      jacobians_abi_layout: bool = False, builtin_model: Optional[str] = None, params=None,
                      return_torch: bool = False, solver: Optional[DeviceSolver] = None, soc: Optional[Dict[str, Any]] = None,
-                     lin_cost_fn=None, cost_fn=None,
+                     lin_cost_fn=None, builtin_cost: Optional[Dict[str, Any]] = None, cost_fn=None,
                      extra_cstrs_fns=None, solver_state=None, filter_method: str = "", debug: bool = False,
                      return_min_viol: bool = False, **ignored):
-    host_only = dict(lin_cost_fn=lin_cost_fn, cost_fn=cost_fn, extra_cstrs_fns=extra_cstrs_fns, solver_state=solver_state,
+    host_only = dict(cost_fn=cost_fn, extra_cstrs_fns=extra_cstrs_fns, solver_state=solver_state,
                      filter_method=filter_method or None, debug=debug or None, return_min_viol=return_min_viol or None)
     bad = [k for k, v in host_only.items() if v is not None]
     if bad:
@@ -72,6 +79,8 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
     lu, uu = (vec(u_l, udim), vec(u_u, udim)) if has(u_l) and has(u_u) else (None, None)
     Qa, Ra = Q.transpose(-1, -2).contiguous(), R.transpose(-1, -2).contiguous()  # ABI: column-major blocks
     sym = bool(torch.equal(Qa, Q) and torch.equal(Ra, R))
+    if (lin_cost_fn is not None or builtin_cost is not None) and not sym:
+        raise ValueError("lin_cost_fn / builtin_cost need symmetric Q and R blocks (the reference shift is a Cholesky solve with them)")
     settings = dict(solver_settings or {})
     solver_name = str(settings.get("solver", "ecos")).lower()  # static_backend.py:242-253
     cone = solver_name in ("ecos", "gurobi", "mosek", "cosmo") or "smooth_cstr" in settings or "smooth_alpha" in settings
@@ -113,6 +122,9 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
     tp = TablePrinter(fields, fmts=["%04d"] + ["%8.3e"] * 5)
     if verbose:
         print(tp.make_header())
+    with_costs = lin_cost_fn is not None or builtin_cost is not None
+    # the built-in cost's descriptor and device arrays: made once, before the loop (nothing of it is uploaded inside)
+    cost_handle = s.prepare_cost(builtin_cost, N, xdim, dev) if builtin_cost is not None else None
     it, max_res = 0, math.inf
     s.stream.wait_stream(torch.cuda.current_stream(dev))  # the set-up above ran on the caller's stream
     while it < max_it:
@@ -127,8 +139,20 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
             else:
                 fxa = fx.reshape(M, N, xdim, xdim).transpose(-1, -2).contiguous()
                 fua = fu.reshape(M, N, xdim, udim).transpose(-1, -2).contiguous()
+        # linearised costs (scp_mpc.py:171-185, 352): this iteration's references; X_ref / U_ref stay as they are for the `obj` column
+        X_ref_, U_ref_ = X_ref, U_ref
+        if builtin_cost is not None:
+            X_ref_ = s.obstacle_cost_grad(X_prev, cost_handle, Q=Qa, X_ref=X_ref_, check=False)
+        if lin_cost_fn is not None:
+            problems = dict(ignored, f=f, fx=fxa, fu=fua, x0=x0, X_prev=X_prev, U_prev=U_prev, Q=Q, R=R, X_ref=X_ref, U_ref=U_ref,
+                            x_l=lx, x_u=ux, u_l=lu, u_u=uu, slew_rate=slew_rate, u0_slew=u0_slew, jacobians_abi_layout=True)
+            cx, cu = lin_cost_fn(X_prev if not single else X_prev[0], U_prev if not single else U_prev[0], problems)
+            if cx is not None:
+                X_ref_ = s.ref_shift(Qa, T(cx).reshape(M, N, xdim).contiguous(), X_ref_, check=False)
+            if cu is not None:
+                U_ref_ = s.ref_shift(Ra, T(cu).reshape(M, N, udim).contiguous(), U_ref, check=False)
         t_aff = time.time()
-        kw = dict(f=f, fx=fxa, fu=fua, X_prev=X_prev, U_prev=U_prev, Q=Qa, R=Ra, X_ref=X_ref, U_ref=U_ref, reg_x=float(reg_x),
+        kw = dict(f=f, fx=fxa, fu=fua, X_prev=X_prev, U_prev=U_prev, Q=Qa, R=Ra, X_ref=X_ref_, U_ref=U_ref_, reg_x=float(reg_x),
                   reg_u=float(reg_u), Nc=Nc, x0=x0c, lx=lx, ux=ux, lu=lu, uu=uu, slew_reg=slew, slew_reg0=slew0, slew_um1=um1,
                   X_out=Xs, U_out=Us, symmetric_cost=sym, verbose=bool(settings.get("verbose", False)),
                   static_cons_bounds=it > 0,  # the boxes are the same in every iteration of this loop (scp_mpc.py:338-376)
@@ -148,6 +172,8 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
         torch.cuda.current_stream(dev).wait_stream(s.stream)
         t_aff = time.time() - t_aff
         if status != 0 or not bool(torch.isfinite(row).all()):  # solver failure (:391-394)
+            if with_costs:  # ... which a Q / R block that is not positive definite causes (NaN references): say so
+                s.check_bad_pivots("lin_cost_fn / builtin_cost: Q or R")
             if verbose:
                 print("Solver failed...")
             return None, None, None
@@ -165,6 +191,8 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
             break
     if verbose:
         print(tp.make_footer())
+    if with_costs:  # the shifts' device-side counter of refused blocks: read once, after the loop
+        s.check_bad_pivots("lin_cost_fn / builtin_cost: Q or R")
     X = torch.cat([x0[:, None, :], X_prev], 1)
     U = U_prev
     if single:
