@@ -284,6 +284,25 @@ int pmpc_linearize_device(pmpc_ctx *ctx, int model, size_t N, size_t M, const do
 int pmpc_linearize_device_f32(pmpc_ctx *ctx, int model, size_t N, size_t M, const double *x0, const double *X_prev,
                               const double *U_prev, const double *params, double *f, float *fx, float *fu);
 
+/* Nonlinear rollout of a built-in model: X[i, j] = F(X[i, j-1], U[i, j]; params[i]) with X[i, -1] = x0[i] — F is the `f` of
+ * pmpc_linearize_device, evaluated alone.  x0 (M, xdim), U (M, N, udim), params (M, ·), X (M, N, xdim), all device, row-major.  A
+ * dynamically feasible iterate for pmpc_scp_loop_device, a plant step (N = 1), the tail of a shifted plan.
+ * Asynchronous on pmpc_stream().  Returns 0; 2 and launches nothing for an unknown model id, N == 0, M == 0 or a null pointer; 1 on a
+ * HIP error. */
+int pmpc_rollout_device(pmpc_ctx *ctx, int model, size_t N, size_t M, const double *x0, const double *U, const double *params, double *X);
+
+/* Receding-horizon shift of a plan by s stages, 1 <= s < N, from (X, U) into (X_new, U_new) — never in place: the two trajectory
+ * buffer pairs of pmpc_scp_loop_device are the intended source and target.
+ *   U_new[i, j] = U[i, j + s],  X_new[i, j] = X[i, j + s]                               for j < N - s
+ *   U_new[i, j] = U_tail[i, j - (N - s)]  (U_tail (M, s, udim); NULL: U[i, N - 1], hold) for j >= N - s
+ *   X_new[i, j] = F(X_new[i, j - 1], U_new[i, j]; params[i])                            for j >= N - s
+ *   um1_new[i]  = U[i, s - 1]  ((M, udim): the control that was applied, for pmpc_problem.slew_um1; NULL: not written)
+ * One launch, asynchronous on pmpc_stream().  Returns 0; 2 and launches nothing for an unknown model id, N == 0, M == 0, s outside
+ * 1 .. N - 1, X_new == X, U_new == U or a null pointer among the others; 1 on a HIP error.  Overlap beyond equal base pointers is
+ * the caller's to avoid. */
+int pmpc_shift_plan_device(pmpc_ctx *ctx, int model, size_t N, size_t M, size_t s, const double *X, const double *U,
+                           const double *params, const double *U_tail, double *X_new, double *U_new, double *um1_new);
+
 /* Compact Jacobian records of a built-in model — what pmpc_scp_loop_device writes into its fx scratch arrays instead of the dense
  * stacks when the coming solve is a warm attempt of the active-set rounds (PMPC_LIN_COMPACT=0 switches that off).  For tests and
  * tools: the linearisation into jc (pmpc_jac_compact_doubles(model, N, M) doubles; f dense), the expansion of jc into the dense

@@ -18,6 +18,15 @@ def scp_solve_device(*args, **kw):
 
     return _impl(*args, **kw)
 
+
+def __getattr__(name):  # (pmpc_amd.MPCController: imported on first use — it needs torch and a HIP device, `import pmpc_amd` does not)
+    if name == "MPCController":
+        from .mpc import MPCController
+
+        return MPCController
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 # keyword-compatible arguments of `solve` (pmpc/__init__.py:5-31)
 SOLVE_KWS = {
     "X_ref", "U_ref", "X_prev", "U_prev", "x_l", "x_u", "u_l", "u_u", "verbose", "debug", "max_it", "time_limit",

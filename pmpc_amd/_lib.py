@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "pmpc_as_sweep_variant",
     "pmpc_ref_shift_device", "pmpc_ref_shift_bad_pivots", "pmpc_obstacle_cost_grad_device", "pmpc_obstacle_ref_shift_device",
     "pmpc_scp_loop_device_cost", "pmpc_abi_scp_cost_size",
+    "pmpc_rollout_device", "pmpc_shift_plan_device",
 ]
 
 
@@ -156,6 +157,11 @@ def load():
         if lib.pmpc_abi_scp_cost_size() != ctypes.sizeof(PmpcScpCost):
             raise ImportError(f"{LIB_PATH} and pmpc_amd/_lib.py disagree on pmpc_scp_cost: library {lib.pmpc_abi_scp_cost_size()} bytes, "
                               f"binding {ctypes.sizeof(PmpcScpCost)}: rebuild the library")
+    if hasattr(lib, "pmpc_shift_plan_device"):  # (likewise: the rollout / plan-shift entry points)
+        lib.pmpc_rollout_device.argtypes = [vp, ctypes.c_int, sz, sz, vp, vp, vp, vp]
+        lib.pmpc_rollout_device.restype = ctypes.c_int
+        lib.pmpc_shift_plan_device.argtypes = [vp, ctypes.c_int, sz, sz, sz] + [vp] * 7
+        lib.pmpc_shift_plan_device.restype = ctypes.c_int
     lib.pmpc_version.argtypes = []
     lib.pmpc_version.restype = ctypes.c_char_p
     # layout check: the library's structs against this binding's mirrors (include/pmpc_abi.h: pmpc_abi_struct_sizes)

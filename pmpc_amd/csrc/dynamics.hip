@@ -20,21 +20,26 @@
 namespace {
 
 struct Unicycle {
-  static constexpr int X = 4, U = 2, UNITS = 64;
+  static constexpr int X = 4, U = 2, P = 3, UNITS = 64;  // (P: parameters per particle)
   typedef jacc::UnicycleSpec Spec;  // which entries of fx / fu the code below makes depend on the state or the control (jac_compact.h)
+  // fo = F(xs, us; p) alone: the `f` of eval, the same expressions in the same order, for k_rollout and k_shift_plan.  A copy on purpose:
+  // with eval calling step the compiler generates other (longer) code for the linearisation kernels, whose outputs are pinned bit for bit
+  static __device__ __forceinline__ void step(const double *xs, const double *us, const double *p, double *fo);
   static __device__ __forceinline__ void eval(long long idx, int N, const double *x0, const double *X_prev, const double *U_prev,
                                               const double *params, double *fo, double *A, double *B);
 };
 struct Quadrotor {
-  static constexpr int X = 12, U = 4, UNITS = 32;  // 32 records of 204 doubles = 52 KB of LDS
+  static constexpr int X = 12, U = 4, P = 4, UNITS = 32;  // 32 records of 204 doubles = 52 KB of LDS
   typedef jacc::QuadrotorSpec Spec;
+  static __device__ __forceinline__ void step(const double *xs, const double *us, const double *p, double *fo);
   static __device__ __forceinline__ void eval(long long idx, int N, const double *x0, const double *X_prev, const double *U_prev,
                                               const double *params, double *fo, double *A, double *B);
 };
 
 struct Bicycle {
-  static constexpr int X = 4, U = 2, UNITS = 64;
+  static constexpr int X = 4, U = 2, P = 2, UNITS = 64;
   typedef jacc::BicycleSpec Spec;
+  static __device__ __forceinline__ void step(const double *xs, const double *us, const double *p, double *fo);
   static __device__ __forceinline__ void eval(long long idx, int N, const double *x0, const double *X_prev, const double *U_prev,
                                               const double *params, double *fo, double *A, double *B);
 };
@@ -48,6 +53,21 @@ void with_model(int model, F &&fn) {
   else throw PmpcHipError{(int)hipErrorInvalidValue, "unknown built-in model", __FILE__, __LINE__};
 }
 
+__device__ __forceinline__ void Unicycle::step(const double *xs, const double *us, const double *p, double *fo) {
+  const double vs = p[0], ws = p[1], T = p[2], eps = 1e-6;
+  double u1 = vs * us[0], u2 = -ws * us[1];
+  u1 += (u1 >= 0.0 ? eps : -eps);
+  u2 += (u2 >= 0.0 ? eps : -eps);
+  const double px = xs[0], py = xs[1], v0 = xs[2], th0 = xs[3];
+  const double a = T * u2 + th0;
+  double sa, ca, s0, c0;
+  sincos(a, &sa, &ca);
+  sincos(th0, &s0, &c0);
+  const double iu2 = 1.0 / u2, iu22 = iu2 * iu2;
+  const double n1 = u2 * sa * v0 + T * u1 * u2 * sa + u1 * ca - s0 * u2 * v0 - c0 * u1;
+  const double n2 = -(u2 * ca * v0 - u1 * sa + T * u1 * u2 * ca) + c0 * u2 * v0 - s0 * u1;
+  fo[0] = px + n1 * iu22; fo[1] = py + n2 * iu22; fo[2] = v0 + T * u1; fo[3] = a;
+}
 __device__ __forceinline__ void Unicycle::eval(long long idx, int N, const double *x0, const double *X_prev, const double *U_prev,
                                                const double *params, double *fo, double *A, double *B) {
   const int i = (int)(idx / N), j = (int)(idx % N);
@@ -84,6 +104,14 @@ __device__ __forceinline__ void Unicycle::eval(long long idx, int N, const doubl
   B[3 + 4 * 1] = T * (-ws);
 }
 
+__device__ __forceinline__ void Bicycle::step(const double *xs, const double *us, const double *p, double *fo) {
+  const double Lw = p[0], dt = p[1];
+  const double px = xs[0], py = xs[1], th = xs[2], v = xs[3], acc = us[0];
+  double s, c;
+  sincos(th, &s, &c);
+  const double td = tan(us[1]), dtv = dt * v;
+  fo[0] = px + dtv * c; fo[1] = py + dtv * s; fo[2] = th + dtv * td / Lw; fo[3] = v + dt * acc;
+}
 __device__ __forceinline__ void Bicycle::eval(long long idx, int N, const double *x0, const double *X_prev, const double *U_prev,
                                               const double *params, double *fo, double *A, double *B) {
   const int i = (int)(idx / N), j = (int)(idx % N);
@@ -106,6 +134,26 @@ __device__ __forceinline__ void Bicycle::eval(long long idx, int N, const double
   B[2 + 4 * 1] = dtv * (1.0 + td * td) / Lw;
 }
 
+__device__ __forceinline__ void Quadrotor::step(const double *xs, const double *us, const double *p, double *fo) {
+  const double m = p[0], Jx = p[1], Jy = p[2], Jz = p[3], dt = 0.05, g = 9.81;
+  const double ph = xs[6], th = xs[7], ps = xs[8], wx = xs[9], wy = xs[10], wz = xs[11];
+  const double T = us[0], tx = us[1], ty = us[2], tz = us[3];
+  double sph, cph, sth, cth, sps, cps;
+  sincos(ph, &sph, &cph);
+  sincos(th, &sth, &cth);
+  sincos(ps, &sps, &cps);
+  const double icth = 1.0 / cth, tth = sth * icth;
+  const double bx = cps * sth * cph + sps * sph, by = sps * sth * cph - cps * sph, bz = cth * cph;
+  const double a = T / m;
+  fo[0] = xs[0] + dt * xs[3]; fo[1] = xs[1] + dt * xs[4]; fo[2] = xs[2] + dt * xs[5];
+  fo[3] = xs[3] + dt * a * bx; fo[4] = xs[4] + dt * a * by; fo[5] = xs[5] + dt * (a * bz - g);
+  fo[6] = ph + dt * (wx + sph * tth * wy + cph * tth * wz);
+  fo[7] = th + dt * (cph * wy - sph * wz);
+  fo[8] = ps + dt * (sph * icth * wy + cph * icth * wz);
+  fo[9] = wx + dt * (tx - (Jz - Jy) * wy * wz) / Jx;
+  fo[10] = wy + dt * (ty - (Jx - Jz) * wz * wx) / Jy;
+  fo[11] = wz + dt * (tz - (Jy - Jx) * wx * wy) / Jz;
+}
 __device__ __forceinline__ void Quadrotor::eval(long long idx, int N, const double *x0, const double *X_prev, const double *U_prev,
                                                 const double *params, double *fo, double *A, double *B) {
   const int i = (int)(idx / N), j = (int)(idx % N);
@@ -305,6 +353,83 @@ __global__ void __launch_bounds__(256) k_widen_f32(const float *src, double *dst
   for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < n; k += (long long)gridDim.x * 256) dst[k] = (double)src[k];
 }
 
+
+// Nonlinear rollout X[i, j] = F(X[i, j-1], U[i, j]; params[i]), X[i, -1] = x0[i]: one lane per particle, the state in registers, N
+// sequential steps.  The chain is latency-bound and there are few particles (64 waves at M = 4096): one wave per block, so that the
+// waves spread over the CUs.  Every lane stores its own stage, X contiguous doubles, lanes N X doubles apart; collecting four stages of
+// the wave's particles in LDS and storing them as 4 X contiguous doubles per particle was measured and dropped (quadrotor, M = 4096,
+// N = 50: 84 us against 43; bicycle: 43 against 36; CHANGELOG.md).
+constexpr int ROLL_LANES = 64;
+template <class Model>
+__global__ void __launch_bounds__(ROLL_LANES) k_rollout(int N, int M, const double *x0, const double *U, const double *params, double *X) {
+  constexpr int XD = Model::X, UD = Model::U, PD = Model::P;
+  const int i = (int)blockIdx.x * ROLL_LANES + (int)threadIdx.x;
+  if (i >= M) return;
+  double x[XD], xn[XD], u[UD], p[PD];
+#pragma unroll
+  for (int k = 0; k < PD; k++) p[k] = params[(size_t)i * PD + k];
+#pragma unroll
+  for (int k = 0; k < XD; k++) x[k] = x0[(size_t)i * XD + k];
+  const double *Ui = U + (size_t)i * N * UD;
+  double *Xi = X + (size_t)i * N * XD;
+  for (int j = 0; j < N; j++) {
+#pragma unroll
+    for (int k = 0; k < UD; k++) u[k] = Ui[(size_t)j * UD + k];
+    Model::step(x, u, p, xn);
+#pragma unroll
+    for (int k = 0; k < XD; k++) Xi[(size_t)j * XD + k] = x[k] = xn[k];
+  }
+}
+
+// Receding-horizon shift by s stages (1 <= s < N) from (X, U) into (Xn, Un), which must not overlap them:
+//   Un[j] = U[j + s], Xn[j] = X[j + s] for j < N - s;  tail j >= N - s: Un[j] = U_tail[i, j - (N - s)] (null: U[N - 1], hold), Xn[j] = F(Xn[j - 1], Un[j]);
+//   um1n[i] = U[i, s - 1] (null: not written).
+// One launch: the first tail_blocks blocks run the s tail steps, one lane per particle (they start from X[N - 1] of the SOURCE, so they wait
+// for no other block); the others copy, element by element, consecutive lanes consecutive doubles.
+template <class Model>
+__global__ void __launch_bounds__(ROLL_LANES) k_shift_plan(int N, int M, int s, int tail_blocks, const double *X, const double *U, const double *params,
+                                                           const double *U_tail, double *Xn, double *Un, double *um1n) {
+  constexpr int XD = Model::X, UD = Model::U, PD = Model::P;
+  const int keep = N - s;
+  if ((int)blockIdx.x < tail_blocks) {
+    const int i = (int)blockIdx.x * ROLL_LANES + (int)threadIdx.x;
+    if (i >= M) return;
+    double x[XD], xn[XD], u[UD], p[PD];
+#pragma unroll
+    for (int k = 0; k < PD; k++) p[k] = params[(size_t)i * PD + k];
+#pragma unroll
+    for (int k = 0; k < XD; k++) x[k] = X[((size_t)i * N + (N - 1)) * XD + k];
+    for (int t = 0; t < s; t++) {
+      const double *us = U_tail ? U_tail + ((size_t)i * s + t) * UD : U + ((size_t)i * N + (N - 1)) * UD;
+#pragma unroll
+      for (int k = 0; k < UD; k++) u[k] = us[k];
+      Model::step(x, u, p, xn);
+#pragma unroll
+      for (int k = 0; k < XD; k++) x[k] = xn[k];
+      const size_t row = (size_t)i * N + keep + t;
+#pragma unroll
+      for (int k = 0; k < UD; k++) Un[row * UD + k] = u[k];
+#pragma unroll
+      for (int k = 0; k < XD; k++) Xn[row * XD + k] = x[k];
+    }
+    return;
+  }
+  const long long nx = (long long)M * keep * XD, nu = (long long)M * keep * UD, nm = um1n ? (long long)M * UD : 0;
+  const long long stride = (long long)((int)gridDim.x - tail_blocks) * ROLL_LANES;
+  for (long long e = (long long)((int)blockIdx.x - tail_blocks) * ROLL_LANES + threadIdx.x; e < nx + nu + nm; e += stride) {
+    if (e < nx) {
+      const long long i = e / (keep * XD), r = e % (keep * XD);
+      Xn[i * N * XD + r] = X[i * N * XD + (long long)s * XD + r];
+    } else if (e < nx + nu) {
+      const long long q = e - nx, i = q / (keep * UD), r = q % (keep * UD);
+      Un[i * N * UD + r] = U[i * N * UD + (long long)s * UD + r];
+    } else {
+      const long long q = e - nx - nu, i = q / UD, k = q % UD;
+      um1n[q] = U[(i * N + (s - 1)) * UD + k];
+    }
+  }
+}
+
 }  // namespace
 
 static long long residual_blocks(long long rows) {
@@ -333,6 +458,22 @@ void launch_linearize_compact(int model, int N, int M, const double *x0, const d
     r.out_bits = (unsigned long long *)res_out;
   }
   with_model(model, [&](auto m) { launch_model_compact<decltype(m)>(N, M, x0, X_prev, U_prev, params, f, jc, r, s); });
+}
+void launch_rollout(int model, int N, int M, const double *x0, const double *U, const double *params, double *X, hipStream_t s) {
+  const unsigned grid = (unsigned)((M + ROLL_LANES - 1) / ROLL_LANES);
+  with_model(model, [&](auto m) { hipLaunchKernelGGL((k_rollout<decltype(m)>), dim3(grid), dim3(ROLL_LANES), 0, s, N, M, x0, U, params, X); });
+}
+void launch_shift_plan(int model, int N, int M, int sh, const double *X, const double *U, const double *params, const double *U_tail, double *Xn,
+                       double *Un, double *um1n, hipStream_t s) {
+  const int tail_blocks = (M + ROLL_LANES - 1) / ROLL_LANES;
+  with_model(model, [&](auto m) {
+    typedef decltype(m) Model;
+    const long long n = (long long)M * (N - sh) * (Model::X + Model::U) + (long long)M * Model::U;
+    long long cb = (n + 4 * ROLL_LANES - 1) / (4 * ROLL_LANES);  // about four elements per lane
+    if (cb > 8192) cb = 8192;
+    hipLaunchKernelGGL((k_shift_plan<Model>), dim3((unsigned)(tail_blocks + cb)), dim3(ROLL_LANES), 0, s, N, M, sh, tail_blocks, X, U, params, U_tail,
+                       Xn, Un, um1n);
+  });
 }
 bool model_known(int model) { return model >= 0 && model <= 2; }
 bool jac_compact_dims(int model, int x, int u) {

@@ -410,6 +410,10 @@ void launch_linearize(int model, int N, int M, const double *x0, const double *X
 void launch_linearize_compact(int model, int N, int M, const double *x0, const double *X_prev, const double *U_prev, const double *params,
                               double *f, double *jc, const double *Xr, const double *Xrp, const double *Ur, const double *Urp, int x, int u,
                               double *res_out, hipStream_t s);
+// nonlinear rollout / receding-horizon shift of a built-in model (include/pmpc_abi.h: pmpc_rollout_device, pmpc_shift_plan_device)
+void launch_rollout(int model, int N, int M, const double *x0, const double *U, const double *params, double *X, hipStream_t s);
+void launch_shift_plan(int model, int N, int M, int sh, const double *X, const double *U, const double *params, const double *U_tail, double *Xn,
+                       double *Un, double *um1n, hipStream_t s);
 bool model_known(int model);                              // a built-in model id (include/pmpc_abi.h)
 bool jac_compact_dims(int model, int x, int u);           // the model has compact records and (x, u) are its dimensions
 long long jac_compact_doubles(int model, int N, int M);  // size of jc (-1: unknown model)

@@ -529,6 +529,31 @@ int pmpc_linearize_device(pmpc_ctx *c, int model, size_t N, size_t M, const doub
   return 0;
 }
 
+// Nonlinear rollout and receding-horizon shift of a built-in model (dynamics.hip): asynchronous on the context's stream.
+int pmpc_rollout_device(pmpc_ctx *c, int model, size_t N, size_t M, const double *x0, const double *U, const double *params, double *X) {
+  if (!c || !model_known(model) || N == 0 || M == 0 || !x0 || !U || !params || !X) return 2;
+  try {
+    HIP_CHECK(hipSetDevice(c->device));
+    launch_rollout(model, (int)N, (int)M, x0, U, params, X, c->stream);
+    HIP_CHECK(hipGetLastError());
+  } catch (const PmpcHipError &) {
+    return 1;
+  }
+  return 0;
+}
+int pmpc_shift_plan_device(pmpc_ctx *c, int model, size_t N, size_t M, size_t s, const double *X, const double *U, const double *params,
+                           const double *U_tail, double *X_new, double *U_new, double *um1_new) {
+  if (!c || !model_known(model) || N == 0 || M == 0 || s < 1 || s >= N || !X || !U || !params || !X_new || !U_new || X_new == X || U_new == U) return 2;
+  try {
+    HIP_CHECK(hipSetDevice(c->device));
+    launch_shift_plan(model, (int)N, (int)M, (int)s, X, U, params, U_tail, X_new, U_new, um1_new, c->stream);
+    HIP_CHECK(hipGetLastError());
+  } catch (const PmpcHipError &) {
+    return 1;
+  }
+  return 0;
+}
+
 // Linearised nonlinear costs (cost_lin.hip).  The counter of refused blocks lives in the workspace, zeroed when it is created.
 static unsigned *cost_bad_counter(pmpc_ctx *c) {
   if (c->ws.cost_bad.ensure(sizeof(unsigned))) HIP_CHECK(hipMemsetAsync(c->ws.cost_bad.p, 0, sizeof(unsigned), c->stream));

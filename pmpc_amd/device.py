@@ -222,6 +222,44 @@ class DeviceSolver:
             raise RuntimeError(f"pmpc_linearize_device failed ({st}): model {model} is not a built-in model, or a HIP error")
         return f, fx, fu
 
+    def rollout(self, model: int, x0, U, params, out=None, wait_current_stream=True):
+        """X (M, N, x) = the nonlinear rollout of a built-in model from x0 (M, x) under U (M, N, u) (pmpc_amd.dynamics.rollout is the
+        specification): X[:, j] = F(X[:, j - 1], U[:, j]; params), the `f` of `linearize` evaluated alone.  `out` must not be `x0`."""
+        self._need("pmpc_rollout_device")
+        M, N, _ = U.shape
+        x = x0.shape[-1]
+        assert x0.shape == (M, x), (x0.shape, U.shape)
+        out = torch.empty((M, N, x), dtype=torch.float64, device=U.device) if out is None else out
+        assert out.shape == (M, N, x)
+        self._before(wait_current_stream)
+        st = self.lib.pmpc_rollout_device(self.h, int(model), N, M, _p(x0), _p(U), _p(params), _p(out))
+        self._after(wait_current_stream)
+        if st != 0:
+            raise RuntimeError(f"pmpc_rollout_device failed ({st}): model {model} is not a built-in model, an empty horizon, or a HIP error")
+        return out
+
+    def shift_plan(self, model: int, X, U, params, s=1, U_tail=None, X_out=None, U_out=None, um1_out=None, wait_current_stream=True):
+        """The receding-horizon shift of a plan by `s` stages, 1 <= s < N (pmpc_amd.dynamics.shift_plan is the specification), in one
+        launch: returns (X', U', um1').  Never in place: `X_out` / `U_out` are other tensors than `X` / `U` (the second trajectory pair
+        of `scp_loop`).  `U_tail` (M, s, u): the controls of the new last s stages, None: the last control is held; their states are
+        rolled out.  um1' = U[:, s - 1] (the control that was applied) is what `slew_um1` of the next solve takes."""
+        self._need("pmpc_shift_plan_device")
+        M, N, x = X.shape
+        u = U.shape[-1]
+        assert U.shape == (M, N, u) and (U_tail is None or U_tail.shape == (M, int(s), u)), (X.shape, U.shape)
+        X_out = torch.empty_like(X) if X_out is None else X_out
+        U_out = torch.empty_like(U) if U_out is None else U_out
+        um1_out = torch.empty((M, u), dtype=torch.float64, device=U.device) if um1_out is None else um1_out
+        assert X_out.shape == X.shape and U_out.shape == U.shape and um1_out.shape == (M, u)
+        if not 1 <= int(s) < N or X_out.data_ptr() == X.data_ptr() or U_out.data_ptr() == U.data_ptr():
+            raise ValueError(f"shift_plan: s = {s} must be in 1 .. N - 1 = {N - 1}, and the shift is not done in place")
+        self._before(wait_current_stream)
+        st = self.lib.pmpc_shift_plan_device(self.h, int(model), N, M, int(s), _p(X), _p(U), _p(params), _p(U_tail), _p(X_out), _p(U_out), _p(um1_out))
+        self._after(wait_current_stream)
+        if st != 0:
+            raise RuntimeError(f"pmpc_shift_plan_device failed ({st}): model {model} is not a built-in model, or a HIP error")
+        return X_out, U_out, um1_out
+
     def linearize_compact(self, model: int, x0, X_prev, U_prev, params, wait_current_stream=True):
         """f (dense) and the compact Jacobian records (one flat tensor) the SCP loop writes for its warm solves."""
         M, N, x = X_prev.shape
@@ -249,7 +287,7 @@ class DeviceSolver:
     # ---- linearised nonlinear costs (csrc/cost_lin.hip) ------------------------------------------------------
     def _need(self, symbol):
         if not hasattr(self.lib, symbol):  # (an older library loaded through PMPC_HIP_LIB: _lib.load leaves the cost prototypes out)
-            raise RuntimeError(f"{_lib.LIB_PATH} has no {symbol}: it predates the linearised-cost entry points, rebuild it (make -C pmpc_amd/csrc)")
+            raise RuntimeError(f"{_lib.LIB_PATH} has no {symbol}: it predates this entry point, rebuild it (make -C pmpc_amd/csrc)")
 
     def check_bad_pivots(self, what):
         """Raise ValueError if a reference shift since the last check met a block that is not positive definite (reads and clears the

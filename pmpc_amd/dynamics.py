@@ -233,6 +233,53 @@ def quadrotor(x, u, p, dt=QUAD_DT):
 
 
 # -------------------------------------------------------------------------------------------------
+# nonlinear rollout and receding-horizon shift of the built-in models (specifications of csrc/dynamics.hip k_rollout, k_shift_plan)
+# -------------------------------------------------------------------------------------------------
+MODEL_NAMES = ("unicycle", "quadrotor", "bicycle")  # position = the model id of include/pmpc_abi.h
+
+
+def model_id(model):
+    """The id of a built-in model given by name or by id."""
+    if isinstance(model, str):
+        if model not in MODEL_NAMES:
+            raise ValueError(f"unknown built-in model {model!r}: one of {MODEL_NAMES}")
+        return MODEL_NAMES.index(model)
+    if int(model) not in range(len(MODEL_NAMES)):
+        raise ValueError(f"unknown built-in model id {model}: 0 .. {len(MODEL_NAMES) - 1}")
+    return int(model)
+
+
+def _model_fn(model):
+    return (unicycle, quadrotor, bicycle)[model_id(model)]
+
+
+def rollout(model, x0, U, params):
+    """X (M, N, x) with X[:, j] = F(X[:, j - 1], U[:, j]; params), X[:, -1] = x0: x0 (M, x), U (M, N, u), params (M, p)."""
+    F = _model_fn(model)
+    x, U, params = np.asarray(x0, float), np.asarray(U, float), np.asarray(params, float)
+    X = np.empty(U.shape[:2] + x.shape[-1:])
+    for j in range(U.shape[1]):
+        x = F(x, U[:, j], params)[0]
+        X[:, j] = x
+    return X
+
+
+def shift_plan(model, X, U, params, s=1, U_tail=None):
+    """The plan (X, U) moved `s` stages on, 1 <= s < N: (X', U', um1') with X'[:, j] = X[:, j + s], U'[:, j] = U[:, j + s] for j < N - s, the
+    last s controls from `U_tail` (M, s, u) (None: U[:, N - 1] held), the last s states rolled out from X[:, N - 1] under them, and
+    um1' = U[:, s - 1], the control that was applied last."""
+    X, U = np.asarray(X, float), np.asarray(U, float)
+    N = U.shape[1]
+    if not 1 <= int(s) < N:
+        raise ValueError(f"shift_plan: s = {s} is outside 1 .. N - 1 = {N - 1}")
+    s = int(s)
+    tail = np.repeat(U[:, N - 1:], s, 1) if U_tail is None else np.asarray(U_tail, float).reshape(U.shape[0], s, U.shape[2])
+    Un = np.concatenate([U[:, s:], tail], 1)
+    Xn = np.concatenate([X[:, s:], rollout(model, X[:, N - 1], tail, params)], 1)
+    return Xn, Un, U[:, s - 1].copy()
+
+
+# -------------------------------------------------------------------------------------------------
 # built-in obstacle cost (include/pmpc_abi.h pmpc_scp_cost; NOT in the reference, whose lin_cost_fn is a user callback)
 # -------------------------------------------------------------------------------------------------
 def _obstacle_arrays(cost, N, xp=np):

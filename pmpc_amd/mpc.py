@@ -1,0 +1,203 @@
+"""Receding-horizon MPC with the problem resident in HBM: `MPCController`.
+
+    ctl = pmpc_amd.MPCController(builtin_model="bicycle", params=P, Q=Q, R=R, X_ref=Xr, U_ref=Ur, u_l=ul, u_u=uu,
+                                 reg_x=1.0, reg_u=1e-2, solver_settings=dict(solver="osqp", Nc=1))
+    while running:
+        u0, info = ctl.step(x0, iterations=3)      # measure x0, shift the plan one stage on, 3 SCP iterations, first control
+
+The constructor uploads the problem once and allocates every buffer of the library's SCP loop (`DeviceSolver.scp_loop`, the loop
+bench.py times); a step is one copy of `x0`, one launch of the plan shift (`DeviceSolver.shift_plan`) and one call of the loop — the
+host reads the per-iteration statuses, the residuals and the first control, nothing else crosses PCIe.
+
+Every step's first SCP iteration runs with `first_cold=True`: after a shift the start iterate is not the previous solve's output, so the
+no-rollout warm start and the compact Jacobian records begin at the second iteration of each step.  (Shifting the solver's active-set
+memory along with the plan is not done.)
+
+Refused with a ValueError (the library loop has no place for them): a Python `f_fx_fu_fn` / `lin_cost_fn` / `cost_fn`, `extra_cstrs_fns`,
+filters, `solver_state`, a sharded context, and `solver_settings` keys other than `solver`, `Nc`, `smooth_alpha`, `slew_reg`,
+`extra_cstrs`, `soc_u_interior`.  `soc=` / `solver_settings["extra_cstrs"]` (one stage-wise second-order cone) are taken as in
+`solve(..., device=...)`; with a stage cone the sub-problem is `lsoc_solve`'s, whatever `solver` says.
+"""
+from __future__ import annotations
+
+import math
+from typing import Any, Dict, Optional
+
+import numpy as np
+import torch
+
+from .device import DeviceSolver
+from .dynamics import model_id
+
+_SETTINGS = ("solver", "Nc", "smooth_alpha", "slew_reg", "extra_cstrs", "soc_u_interior")
+_CONE_SOLVERS = ("ecos", "gurobi", "mosek", "cosmo")
+
+
+class MPCController:
+    def __init__(self, builtin_model=None, params=None, Q=None, R=None, X_ref=None, U_ref=None, u_l=None, u_u=None, x_l=None, x_u=None,
+                 reg_x: float = 1e0, reg_u: float = 1e-2, solver_settings: Optional[Dict[str, Any]] = None, builtin_cost: Optional[Dict[str, Any]] = None,
+                 slew_rate: Optional[float] = None, u0_slew=None, soc: Optional[Dict[str, Any]] = None, device="cuda",
+                 solver: Optional[DeviceSolver] = None, **unsupported):
+        if builtin_model is None:
+            raise ValueError("MPCController needs builtin_model=: a Python f_fx_fu_fn cannot enter the library's SCP loop")
+        bad = [k for k, v in unsupported.items() if v is not None and v != ""]
+        if bad:
+            raise ValueError(f"MPCController does not support {sorted(bad)}; the host loop pmpc_amd.solve(...) has the host-only features")
+        settings = dict(solver_settings or {})
+        bad = [k for k in settings if k not in _SETTINGS]
+        if bad:
+            raise ValueError(f"MPCController: solver_settings {sorted(bad)} are not taken by the library's SCP loop (taken: {_SETTINGS})")
+        if params is None or Q is None or R is None:
+            raise ValueError("MPCController needs params=, Q= and R=")
+        self.model = model_id(builtin_model)
+        dev = torch.device(device)
+        self.device = dev
+        T = lambda z: torch.as_tensor(np.asarray(z) if not torch.is_tensor(z) else z, dtype=torch.float64, device=dev)
+        Q, R = T(Q), T(R)
+        if Q.ndim != 4 or R.ndim != 4:
+            raise ValueError("MPCController: Q (M, N, x, x) and R (M, N, u, u)")
+        M, N, x, u = Q.shape[0], Q.shape[1], Q.shape[-1], R.shape[-1]
+        self.M, self.N, self.xdim, self.udim = M, N, x, u
+        if solver is None:
+            from .scp_device import _solver_for
+
+            solver = _solver_for(dev)
+        if solver.world > 1:
+            raise ValueError("MPCController: a sharded context (comm_world > 1) is not supported")
+        self.solver = s = solver
+        vec = lambda z, d: T(z).reshape(M, N, d).contiguous().clone()
+        has = lambda z: z is not None and (z.numel() if torch.is_tensor(z) else np.size(z)) > 0
+        Qa, Ra = Q.transpose(-1, -2).contiguous(), R.transpose(-1, -2).contiguous()  # ABI: column-major blocks
+        sym = bool(torch.equal(Qa, Q) and torch.equal(Ra, R))
+        if builtin_cost is not None and not sym:
+            raise ValueError("builtin_cost needs symmetric Q and R blocks (the reference shift is a Cholesky solve with them)")
+        self.X_ref = torch.zeros((M, N, x), dtype=torch.float64, device=dev) if X_ref is None else vec(X_ref, x)
+        self.U_ref = torch.zeros((M, N, u), dtype=torch.float64, device=dev) if U_ref is None else vec(U_ref, u)
+        lx, ux = (vec(x_l, x), vec(x_u, x)) if has(x_l) and has(x_u) else (None, None)
+        lu, uu = (vec(u_l, u), vec(u_u, u)) if has(u_l) and has(u_u) else (None, None)
+        self.params = T(params).reshape(M, -1).contiguous().clone()
+        solver_name = str(settings.get("solver", "ecos")).lower()
+        cone = solver_name in _CONE_SOLVERS or "smooth_alpha" in settings
+        alpha = float(settings.get("smooth_alpha", math.nan))
+        Nc = int(settings.get("Nc", -1))
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        slew = torch.full((M,), float(slew_rate), dtype=torch.float64, device=dev) if slew_rate is not None and float(slew_rate) != 0.0 else None
+        # slew_reg: the penalty on U[0] - (the control applied last); that control is u0_slew before the first step (None: the first
+        # step has no such term, as solve(..., u0_slew=None)) and the shift's um1' from then on
+        self._slew0 = torch.full((M,), float(settings["slew_reg"]), dtype=torch.float64, device=dev) if "slew_reg" in settings else None
+        self._um1 = mk(M, u) if self._slew0 is not None else None
+        self._u0_slew = None if u0_slew is None or self._um1 is None else T(u0_slew).reshape(-1, u).expand(M, u).contiguous()
+        soc_kw = {}
+        if soc is None and settings.get("extra_cstrs"):  # the reference's tuple format, stage-wise SOC case only (as scp_device.py)
+            from .extra_cstrs import stage_soc_from_extra_cstrs
+
+            tuples = list(settings["extra_cstrs"])
+            if len(tuples) != 1:
+                raise ValueError("one extra_cstrs tuple (the stage-wise second-order cone) is supported")
+            soc = stage_soc_from_extra_cstrs(tuples[0], M, N, x, u, Nc)
+            if "soc_u_interior" not in settings:
+                raise ValueError("solver_settings['soc_u_interior'] (a control strictly inside the boxes and the cone) is required")
+            soc["u_interior"] = settings["soc_u_interior"]
+        if soc is not None:
+            soc_kw = dict(soc_W=T(soc["W"]).reshape(-1, u).contiguous(), soc_w0=T(soc["w0"]).reshape(-1).contiguous(),
+                          soc_v=T(soc["v"]).reshape(u).contiguous(), soc_v0=float(soc.get("v0", 0.0)),
+                          soc_u_interior=T(soc["u_interior"]).reshape(u).contiguous())
+        elif cone:  # as bench.py drives the cone objective through the loop (smoothing: barrier_mu = 1 / alpha)
+            soc_kw = dict(cone_objective=True, barrier_mu=0.0 if math.isnan(alpha) else 1.0 / alpha)
+        self._x0 = mk(M, x)
+        self._pairs = [(mk(M, N, x), mk(M, N, u)), (mk(M, N, x), mk(M, N, u))]  # the two trajectory pairs of the loop
+        self._lin = [mk(M, N, x), mk(M, N, x, x), mk(M, N, u, x), mk(M, N, x), mk(M, N, x, x), mk(M, N, u, x)]  # f, fx, fu; f2, fx2, fu2
+        self._res = mk(64)
+        self._cost = s.prepare_cost(builtin_cost, N, x, dev) if builtin_cost is not None else None
+        self._kw = dict(Q=Qa, R=Ra, X_ref=self.X_ref, U_ref=self.U_ref, reg_x=float(reg_x), reg_u=float(reg_u), Nc=Nc, x0=self._x0, lx=lx, ux=ux,
+                        lu=lu, uu=uu, slew_reg=slew, symmetric_cost=sym, **soc_kw)
+        torch.cuda.current_stream(dev).synchronize()  # (the uploads above ran on the caller's stream; the kernels read them on the solver's)
+        self.reset()
+
+    # ---- the plan -------------------------------------------------------------------------------------------
+    @property
+    def X(self):
+        """The current plan's states (M, N, x): stage j is the state after j + 1 steps (a GPU tensor, overwritten by the next step)."""
+        return self._pairs[self._cur][0]
+
+    @property
+    def U(self):
+        return self._pairs[self._cur][1]
+
+    def _load(self, dst, src):
+        src = torch.as_tensor(np.asarray(src) if not torch.is_tensor(src) else src, dtype=torch.float64)
+        dst.copy_(src.to(self.device).reshape(dst.shape))
+
+    def reset(self, X_prev=None, U_prev=None, rollout: bool = False):
+        """Start over from the iterate (X_prev, U_prev) — None: X_ref / U_ref, the defaults of `solve` — with no plan to shift: the
+        next `step` solves from it as it is.  `rollout=True`: the next step replaces X_prev by the rollout of its x0 under U_prev, a
+        dynamically feasible start.  Clears a failure."""
+        s = self.solver
+        s._before()
+        with torch.cuda.stream(s.stream):
+            self._cur = 0
+            self._load(self._pairs[0][0], self.X_ref if X_prev is None else X_prev)
+            self._load(self._pairs[0][1], self.U_ref if U_prev is None else U_prev)
+            if self._u0_slew is not None:
+                self._um1.copy_(self._u0_slew)
+        s._after()
+        self._um1_valid = self._u0_slew is not None
+        self._fresh, self._rollout, self.failed = True, bool(rollout), False
+
+    def set_reference(self, X_ref=None, U_ref=None):
+        """New references (M, N, x) / (M, N, u), copied into the resident buffers (None: unchanged)."""
+        s = self.solver
+        s._before()
+        with torch.cuda.stream(s.stream):
+            if X_ref is not None:
+                self._load(self.X_ref, X_ref)
+            if U_ref is not None:
+                self._load(self.U_ref, U_ref)
+        s._after()
+
+    # ---- one MPC step ----------------------------------------------------------------------------------------
+    def step(self, x0, iterations: int = 3, shift: int = 1, U_tail=None, return_torch: bool = False):
+        """x0 (x,) or (M, x), numpy or GPU tensor -> (u0, info): u0 = U[:, 0, :] of the new plan, a copy (M, u) (numpy unless
+        `return_torch`); info = dict(resid=per-iteration SCP residuals, infos=per-iteration solver infos, status=, iterations_done=).
+        On every call but the first after `reset` the previous plan is first moved `shift` stages on (`U_tail` (M, shift, u): the new
+        last controls, None: hold).  A failed sub-problem returns (None, info); the controller then refuses `step` until `reset()`."""
+        if self.failed:
+            raise RuntimeError("MPCController.step: the previous step failed (info['status'] != 0); call reset() first")
+        iterations = int(iterations)
+        if not 1 <= iterations <= self._res.numel():
+            raise ValueError(f"MPCController.step: iterations = {iterations} is outside 1 .. {self._res.numel()}")
+        s = self.solver
+        s._before()  # x0 (and U_tail) may come from the caller's stream; everything below is on the solver's
+        with torch.cuda.stream(s.stream):
+            x0 = torch.as_tensor(np.asarray(x0) if not torch.is_tensor(x0) else x0, dtype=torch.float64)
+            self._x0.copy_(x0.to(self.device).reshape(-1, self.xdim).expand(self.M, self.xdim))
+            if U_tail is not None:
+                U_tail = torch.as_tensor(np.asarray(U_tail) if not torch.is_tensor(U_tail) else U_tail, dtype=torch.float64).to(self.device).contiguous()
+        if self._fresh:
+            if self._rollout:
+                s.rollout(self.model, self._x0, self.U, self.params, out=self.X, wait_current_stream=False)
+        else:
+            Xn, Un = self._pairs[self._cur ^ 1]
+            s.shift_plan(self.model, self.X, self.U, self.params, s=shift, U_tail=U_tail, X_out=Xn, U_out=Un, um1_out=self._um1,
+                         wait_current_stream=False)
+            self._cur ^= 1
+            self._um1_valid = self._um1 is not None
+        self._fresh = False
+        slew0 = dict(slew_reg0=self._slew0, slew_um1=self._um1) if self._um1_valid else {}
+        (Xa, Ua), (Xb, Ub) = self._pairs[self._cur], self._pairs[self._cur ^ 1]
+        f, fx, fu, f2, fx2, fu2 = self._lin
+        res, infos, last_in_out, done = s.scp_loop(self.model, self.params, iterations, f=f, fx=fx, fu=fu, f2=f2, fx2=fx2, fu2=fu2, X_prev=Xa, U_prev=Ua,
+                                                   X_out=Xb, U_out=Ub, first_cold=True, res=self._res[:iterations], cost=self._cost,
+                                                   wait_current_stream=False, **slew0, **self._kw)
+        if last_in_out:
+            self._cur ^= 1
+        ok = done == iterations
+        with torch.cuda.stream(s.stream):
+            resid = res[:done].cpu().numpy()  # (synchronises the solver's stream)
+            u0 = self.U[:, 0, :].clone() if ok else None
+        s._after()
+        info = dict(resid=resid, infos=infos, status=0 if ok else int(infos[-1]["status"]), iterations_done=int(done))
+        if not ok:
+            self.failed = True
+            return None, info
+        return (u0 if return_torch else u0.cpu().numpy()), info

@@ -1,0 +1,115 @@
+#!/usr/bin/env python
+"""What a closed-loop MPC step costs: `MPCController.step` against repeated `pmpc_amd.solve(..., device="cuda")` calls with a warm start
+shifted on the host, and the launch times of the rollout / plan-shift kernels next to one linearisation launch.  Not a benchmark of the
+solver (bench.py is); the numbers of CHANGELOG.md's MPCController entry come from here.
+
+    python tools/mpc_step_time.py --model quadrotor --M 4096 --N 50 --steps 50 --iterations 3
+
+Kernel times: HIP events on the solver's stream around single launches, all shapes warmed first, the kernels alternating in one loop.
+Step times: host clock around calls that end with a device->host read (both are synchronous), the two versions alternating step by step
+on the same sequence of measured states.  Prints one JSON line."""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+
+
+def _stats(v):
+    v = np.asarray(v, float)
+    return dict(median=float(np.median(v)), min=float(v.min()), max=float(v.max()), p10=float(np.percentile(v, 10)), p90=float(np.percentile(v, 90)))
+
+
+def kernel_times(solver, mid, d, reps=30):
+    """Median / spread in microseconds of one launch of rollout, shift_plan (s = 1) and linearize."""
+    import torch
+
+    X, U = d["X_prev"], d["U_prev"]
+    Xo, Uo, um1 = torch.empty_like(X), torch.empty_like(U), torch.empty((U.shape[0], U.shape[2]), dtype=torch.float64, device=U.device)
+    f, fx, fu = solver.linearize(mid, d["x0"], X, U, d["params"])
+    jobs = {"rollout": lambda: solver.rollout(mid, d["x0"], U, d["params"], out=Xo, wait_current_stream=False)}
+    jobs["shift_plan"] = lambda: solver.shift_plan(mid, X, U, d["params"], s=1, X_out=Xo, U_out=Uo, um1_out=um1, wait_current_stream=False)
+    jobs["linearize"] = lambda: solver.linearize(mid, d["x0"], X, U, d["params"], f, fx, fu, wait_current_stream=False)
+    out = {k: [] for k in jobs}
+    with torch.cuda.stream(solver.stream):
+        for rep in range(reps + 5):
+            for k, job in jobs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                job()
+                e1.record()
+                e1.synchronize()
+                if rep >= 5:  # (the first five rounds warm every kernel)
+                    out[k].append(1e3 * e0.elapsed_time(e1))
+    return {k: _stats(v) for k, v in out.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--model", default="bicycle", choices=["unicycle", "quadrotor", "bicycle"])
+    ap.add_argument("--M", type=int, default=256)
+    ap.add_argument("--N", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=50, help="timed MPC steps per version (after --warmup)")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--iterations", type=int, default=3)
+    ap.add_argument("--no-solve", action="store_true", help="leave the pmpc_amd.solve version out (kernel times and the controller only)")
+    args = ap.parse_args()
+
+    import pmpc_amd
+    from pmpc_amd import dynamics as dyn
+    from pmpc_amd.device import DeviceSolver, to_device_problem
+
+    prob = getattr(dyn, f"make_{args.model}_problem")(M=args.M, N=args.N, Nc=1)
+    mid = dyn.model_id(args.model)
+    F = getattr(dyn, args.model)
+    solver = DeviceSolver(0)
+    result = dict(model=args.model, M=args.M, N=args.N, iterations=args.iterations, steps=args.steps)
+    result["kernel_us"] = kernel_times(solver, mid, to_device_problem(prob))
+
+    common = dict(X_ref=prob["X_ref"], U_ref=prob["U_ref"], u_l=prob["u_l"], u_u=prob["u_u"], reg_x=prob["reg_x"], reg_u=prob["reg_u"],
+                  solver_settings=dict(solver="osqp", Nc=1))
+    ctl = pmpc_amd.MPCController(builtin_model=args.model, params=prob["params"], Q=prob["Q"], R=prob["R"], solver=solver, **common)
+    ctl.reset(X_prev=prob["X_prev"], U_prev=prob["U_prev"])
+    Xs, Us = prob["X_prev"], prob["U_prev"]  # the solve version's warm start
+    rng = np.random.default_rng(0)
+    x0 = prob["x0"][0]
+    t_ctl, t_solve, first, later = [], [], [], []
+    for k in range(args.warmup + args.steps):
+        t0 = time.perf_counter()
+        u0, info = ctl.step(x0, iterations=args.iterations)
+        t1 = time.perf_counter()
+        if u0 is None:
+            raise SystemExit(f"MPCController.step failed in step {k}: {info}")
+        if not args.no_solve:
+            t2 = time.perf_counter()
+            if k > 0:
+                Xs, Us, _ = dyn.shift_plan(mid, Xs, Us, prob["params"], s=1)
+            X, U, data = pmpc_amd.solve(None, prob["Q"], prob["R"], np.tile(x0, (args.M, 1)), device="cuda", builtin_model=args.model, params=prob["params"],
+                                        X_prev=Xs, U_prev=Us, max_it=args.iterations, res_tol=0.0, verbose=False, **common)  # (on the package's own context)
+            t3 = time.perf_counter()
+            if X is None:
+                raise SystemExit(f"pmpc_amd.solve failed in step {k}")
+            Xs, Us = X[:, 1:], U
+        if k >= args.warmup:
+            t_ctl.append(1e3 * (t1 - t0))
+            if not args.no_solve:
+                t_solve.append(1e3 * (t3 - t2))
+            first.append((info["infos"][0]["active_set_rounds"], info["infos"][0]["ipm_iters"]))
+            later += [(i["active_set_rounds"], i["ipm_iters"]) for i in info["infos"][1:]]
+        x0 = F(x0, u0[0], prob["params"][0])[0] + 0.01 * rng.standard_normal(x0.shape)
+    result["controller_step_ms"] = _stats(t_ctl)
+    if t_solve:
+        result["solve_step_ms"] = _stats(t_solve)
+    mean = lambda rows, c: float(np.mean([r[c] for r in rows])) if rows else float("nan")
+    result["first_iteration"] = dict(active_set_rounds=mean(first, 0), ipm_iters=mean(first, 1))
+    result["later_iterations"] = dict(active_set_rounds=mean(later, 0), ipm_iters=mean(later, 1))
+    solver.close()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
