@@ -391,6 +391,36 @@ int pmpc_scp_loop_device_cost(pmpc_ctx *ctx, int model, const double *params, co
                               double *fu2, int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out,
                               const pmpc_scp_cost *cost);
 
+/* A built-in constraint for loops that have no Python callable.  kind 1, keep-out: every stage j = 0 .. N-1 (0-based: the state after
+ * j + 1 steps, row j of X_prev) of every particle i stays outside K balls, 1 <= K <= 4, in the position sub-space pos_idx (pos_dim = 2 or
+ * 3 distinct state indices):  |X[i, j, pos_idx] - c_ijk| >= r_k.  About the previous iterate the SCP loop imposes the half-space
+ *   n'(p - c) >= r,  n = (pbar - c) / |pbar - c|,  pbar = X_prev[i, j, pos_idx]   (n = the first position axis if |pbar - c| < 1e-12),
+ * i.e. the row a_x'x <= h with a_x[pos_idx] = -n, h = -r - n'c; every point of it is outside the ball (Cauchy-Schwarz).
+ * centres (device): centre k of (particle i, stage j) is at centres + i centre_stride_particle + j centre_stride_stage + k pos_dim
+ * (strides in doubles, >= 0: (0, 0) static obstacles (K, pos_dim); (0, K pos_dim) moving ones (N, K, pos_dim); (N K pos_dim, K pos_dim)
+ * per particle and stage (M, N, K, pos_dim)); radius (device): (K). */
+typedef struct pmpc_scp_cstr {
+  int kind; /* 0 none, 1 keep-out */
+  int K, pos_dim;
+  int pos_idx[3];
+  long long centre_stride_particle, centre_stride_stage;
+  const double *centres, *radius;
+} pmpc_scp_cstr;
+size_t pmpc_abi_scp_cstr_size(void); /* sizeof(pmpc_scp_cstr) as the library was built (see pmpc_abi_struct_sizes) */
+
+/* The linearised problem with the K rows of every (particle, stage) restated as upper bounds on K auxiliary states that the linearised
+ * dynamics produce (state dimension xd = xdim + K; pmpc_amd/extra_cstrs.py keepout_augment is the specification), one launch:
+ *   f_aug (M, N, xd)          [f | a_k'f]                       X_prev_aug (M, N, xd)  [X_prev | 0]
+ *   fx_aug (M, N, xd, xd)     rows >= xdim: a_k'fx, columns >= xdim: 0     X_ref_aug (M, N, xd)   [X_ref | 0]; not written if X_ref is NULL
+ *   fu_aug (M, N, udim, xd)   rows >= xdim: a_k'fu              xu_aug (M, N, xd)      entries xdim + k <- h_k; the first xdim are NOT written
+ * in the layouts above (blocks column-major).  The parts that do not change with the iterate (Q with -reg_x on the auxiliary diagonal,
+ * x0, the lower bounds -inf, the first xdim upper bounds) are the caller's.  Inputs and outputs must not overlap.  Asynchronous on
+ * pmpc_stream().  Returns 0; 2 and launches nothing for K outside 1 .. 4, a bad pos_dim or pos_idx, xdim + K > 16, udim outside
+ * 1 .. 16, a negative stride, N == 0, M == 0 or a null pointer (X_ref may be NULL, and X_ref_aug with it); 1 on a HIP error. */
+int pmpc_keepout_augment_device(pmpc_ctx *ctx, const pmpc_scp_cstr *cstr, size_t xdim, size_t udim, size_t N, size_t M,
+                                const double *X_prev, const double *f, const double *fx, const double *fu, const double *X_ref,
+                                double *f_aug, double *fx_aug, double *fu_aug, double *X_prev_aug, double *X_ref_aug, double *xu_aug);
+
 /* Live kernel timing for bench.py: HIP events on pmpc_stream() around the launches of a class
  * (0 backward+factor, 1 backward vector-only, 2 forward, 3 consensus reduce+solve).
  * level 0 = off, 1 = class 0 only (the dominant kernel; what bench.py's roofline needs), 2 = every class

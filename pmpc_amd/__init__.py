@@ -10,6 +10,7 @@ from .scp_mpc import AA_method, FILTER_MAP, aff_solve, scp_solve, select_method,
 from .backend import is_precompiled_backend_available, lcone_solve, lqp_solve  # noqa: F401
 from .problem_struct import Problem  # noqa: F401
 from .problem_matrices import lqp_generate_problem_matrices  # noqa: F401
+from .extra_cstrs import keepout_augment, keepout_rows, make_keepout_extra_cstrs_fn  # noqa: F401
 
 
 def scp_solve_device(*args, **kw):

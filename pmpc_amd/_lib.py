@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "pmpc_ref_shift_device", "pmpc_ref_shift_bad_pivots", "pmpc_obstacle_cost_grad_device", "pmpc_obstacle_ref_shift_device",
     "pmpc_scp_loop_device_cost", "pmpc_abi_scp_cost_size",
     "pmpc_rollout_device", "pmpc_shift_plan_device",
+    "pmpc_keepout_augment_device", "pmpc_abi_scp_cstr_size",
 ]
 
 
@@ -57,6 +58,13 @@ class PmpcScpCost(ctypes.Structure):
     """pmpc_scp_cost (include/pmpc_abi.h): the built-in cost of pmpc_scp_loop_device_cost."""
     _fields_ = [("kind", ctypes.c_int), ("K", ctypes.c_int), ("pos_dim", ctypes.c_int), ("pos_idx", ctypes.c_int * 3), ("per_stage", ctypes.c_int),
                 ("centres", ctypes.c_void_p), ("sigma", ctypes.c_void_p), ("w", ctypes.c_void_p)]
+
+
+class PmpcScpCstr(ctypes.Structure):
+    """pmpc_scp_cstr (include/pmpc_abi.h): the built-in constraint of pmpc_keepout_augment_device."""
+    _fields_ = [("kind", ctypes.c_int), ("K", ctypes.c_int), ("pos_dim", ctypes.c_int), ("pos_idx", ctypes.c_int * 3),
+                ("centre_stride_particle", ctypes.c_longlong), ("centre_stride_stage", ctypes.c_longlong),
+                ("centres", ctypes.c_void_p), ("radius", ctypes.c_void_p)]
 
 
 def load():
@@ -162,6 +170,14 @@ def load():
         lib.pmpc_rollout_device.restype = ctypes.c_int
         lib.pmpc_shift_plan_device.argtypes = [vp, ctypes.c_int, sz, sz, sz] + [vp] * 7
         lib.pmpc_shift_plan_device.restype = ctypes.c_int
+    if hasattr(lib, "pmpc_keepout_augment_device"):  # (likewise: the keep-out constraint)
+        lib.pmpc_keepout_augment_device.argtypes = [vp, ctypes.POINTER(PmpcScpCstr), sz, sz, sz, sz] + [vp] * 11
+        lib.pmpc_keepout_augment_device.restype = ctypes.c_int
+        lib.pmpc_abi_scp_cstr_size.argtypes = []
+        lib.pmpc_abi_scp_cstr_size.restype = sz
+        if lib.pmpc_abi_scp_cstr_size() != ctypes.sizeof(PmpcScpCstr):
+            raise ImportError(f"{LIB_PATH} and pmpc_amd/_lib.py disagree on pmpc_scp_cstr: library {lib.pmpc_abi_scp_cstr_size()} bytes, "
+                              f"binding {ctypes.sizeof(PmpcScpCstr)}: rebuild the library")
     lib.pmpc_version.argtypes = []
     lib.pmpc_version.restype = ctypes.c_char_p
     # layout check: the library's structs against this binding's mirrors (include/pmpc_abi.h: pmpc_abi_struct_sizes)

@@ -1,0 +1,14 @@
+// keepout.h — launcher of keepout.hip (keep-out constraints of the SCP loop: obstacle half-spaces restated as bounds on auxiliary states)
+#pragma once
+#include "../../include/pmpc_abi.h"
+#include "pmpc_dev.h"
+
+constexpr int KEEPOUT_MAX_K = 4;
+constexpr int KEEPOUT_MAX_DIM = 16;  // xdim + K, the largest state dimension the solver's kernels take
+
+// a kind-1 description the kernel can run for this state dimension
+bool keepout_cstr_valid(const pmpc_scp_cstr *cstr, int xdim);
+// the augmented linearisation of M N (particle, stage) units in one launch; X_ref null: X_ref_aug is not written
+void launch_keepout_augment(const pmpc_scp_cstr &cstr, int x, int u, int N, int M, const double *X_prev, const double *f, const double *fx,
+                            const double *fu, const double *X_ref, double *f_aug, double *fx_aug, double *fu_aug, double *X_prev_aug,
+                            double *X_ref_aug, double *xu_aug, hipStream_t s);

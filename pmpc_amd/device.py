@@ -366,6 +366,57 @@ class DeviceSolver:
         del keep  # (the cost's device arrays: the launch is done, or the caller's stream — where torch reuses their memory — waits for it)
         return out
 
+    # ---- keep-out constraints (csrc/keepout.hip) ---------------------------------------------------------------
+    def prepare_cstr(self, cstr, M, N, x, device="cuda"):
+        """A handle of a built-in constraint dict(kind="keepout", pos_idx=, centres=, radius=) for repeated `keepout_augment` calls on
+        (M particles, N stages, x states): the descriptor and its device arrays, uploaded once.  centres: (K, pos_dim) static,
+        (N, K, pos_dim) per stage, (M, N, K, pos_dim) per particle and stage.  A handle passes through."""
+        self._need("pmpc_keepout_augment_device")
+        if isinstance(cstr, tuple):
+            return cstr
+        from .extra_cstrs import _keepout_arrays
+
+        class _xp:
+            asarray = staticmethod(lambda a: torch.as_tensor(a, dtype=torch.float64, device=device))
+
+        pos_idx, cen, rad = _keepout_arrays(cstr, M, N, x, _xp)
+        K, pd = int(rad.shape[0]), len(pos_idx)
+        if x + K > 16:
+            raise ValueError(f"keep-out constraint: {x} states + {K} auxiliary states exceed the solver's 16")
+        stride_p = N * K * pd if cen.shape[0] != 1 else 0
+        stride_s = K * pd if cen.shape[1] != 1 or cen.shape[0] != 1 else 0
+        keep = [cen.contiguous(), rad.contiguous()]
+        torch.cuda.current_stream(self.device).synchronize()  # (they were just uploaded on the caller's stream; the kernel reads them on the solver's)
+        sc = _lib.PmpcScpCstr(kind=1, K=K, pos_dim=pd, pos_idx=(ctypes.c_int * 3)(*pos_idx), centre_stride_particle=stride_p,
+                              centre_stride_stage=stride_s, centres=keep[0].data_ptr(), radius=keep[1].data_ptr())
+        return sc, keep
+
+    def keepout_augment(self, cstr, X_prev, f, fx, fu, X_ref=None, out=None, wait_current_stream=True):
+        """The linearisation (f, fx, fu: ABI layout) with the keep-out rows about X_prev restated as upper bounds on K auxiliary states
+        (pmpc_amd.extra_cstrs.keepout_augment is the specification), one launch: returns dict(f (M, N, xd), fx (M, N, xd, xd),
+        fu (M, N, u, xd), X_prev (M, N, xd), X_ref (M, N, xd), xu (M, N, xd)), xd = x + K.  Of `xu` only the K auxiliary entries of every
+        stage are written (the rows' right-hand sides); `X_ref` is written if an X_ref is given.  `out`: the same dict, preallocated."""
+        M, N, x = X_prev.shape
+        u = fu.shape[-2]
+        sc, keep = self.prepare_cstr(cstr, M, N, x, X_prev.device)
+        xd = x + sc.K
+        assert f.shape == (M, N, x) and fx.shape == (M, N, x, x) and fu.shape == (M, N, u, x) and (X_ref is None or X_ref.shape == (M, N, x))
+        if out is None:
+            mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=X_prev.device)
+            out = dict(f=mk(M, N, xd), fx=mk(M, N, xd, xd), fu=mk(M, N, u, xd), X_prev=mk(M, N, xd), X_ref=mk(M, N, xd), xu=mk(M, N, xd))
+        for k, shape in (("f", (M, N, xd)), ("fx", (M, N, xd, xd)), ("fu", (M, N, u, xd)), ("X_prev", (M, N, xd)), ("X_ref", (M, N, xd)), ("xu", (M, N, xd))):
+            assert out[k].shape == shape, (k, out[k].shape, shape)
+        self._before(wait_current_stream)
+        st = self.lib.pmpc_keepout_augment_device(self.h, ctypes.byref(sc), x, u, N, M, _p(X_prev), _p(f), _p(fx), _p(fu), _p(X_ref), _p(out["f"]),
+                                                  _p(out["fx"]), _p(out["fu"]), _p(out["X_prev"]), _p(out["X_ref"]), _p(out["xu"]))
+        self._after(wait_current_stream)
+        if st != 0:
+            raise RuntimeError(f"pmpc_keepout_augment_device failed ({st})")
+        if not wait_current_stream:
+            self.sync()
+        del keep  # (the constraint's device arrays: the launch is done, or the caller's stream — where torch reuses their memory — waits for it)
+        return out
+
     def scp_residual(self, X, X_prev, U, U_prev, out=None, wait_current_stream=True):
         """max(max_ij ||X - X_prev||_2, max_ij ||U - U_prev||_2) of pmpc/scp_mpc.py:397-403 as a one-element device tensor
         (one fused pass on the solver's stream; inf if a trajectory holds a NaN)."""
@@ -386,6 +437,9 @@ class DeviceSolver:
         (else in (X_prev, U_prev)), iterations completed.  `cost=dict(kind="obstacles", pos_idx=, centres=, sigma=, w=)`: the built-in
         obstacle cost (`obstacle_cost_grad`) is linearised about every iterate and the sub-problem tracks X_ref - Q^-1 cx (float64 Q
         with symmetric positive definite blocks; refused with status 2 next to float32 matrices)."""
+        if kw.pop("builtin_cstr", None) is not None:
+            raise ValueError("scp_loop: builtin_cstr is not supported (the library loop has one fixed state dimension, compact Jacobian records and "
+                             "the no-rollout warm start; solve(..., device=..., builtin_cstr=...) carries the constraint)")
         prob, X_out, U_out = self._problem(**kw)
         res = torch.empty((steps,), dtype=torch.float64, device=f2.device) if res is None else res
         infos = (_lib.PmpcInfo * steps)()

@@ -360,3 +360,106 @@ def split_linear_cost(cstr: Sequence[Any], M: int, N: int, xdim: int, udim: int,
     cx = full[ncu:].reshape(M, N, xdim)
     return cu, cx, (l, q, e, G_left, G_right, h, np.zeros(cl.size), c_right)
 
+
+
+# -------------------------------------------------------------------------------------------------
+# built-in keep-out constraint (include/pmpc_abi.h pmpc_scp_cstr; specification of csrc/keepout.hip k_keepout_augment)
+# -------------------------------------------------------------------------------------------------
+KEEPOUT_DEGENERATE = 1e-12  # |pbar - c| below this: the direction is the first position axis
+
+
+def _keepout_arrays(cstr, M, N, xdim=None, xp=np):
+    """(pos_idx list, centres broadcastable to (M, N, K, pos_dim) as a 4-d array, radius (K,)) of dict(kind="keepout", pos_idx=, centres=,
+    radius=): centres (K, pos_dim) static, (N, K, pos_dim) per stage, (M, N, K, pos_dim) per particle and stage."""
+    if cstr.get("kind", "keepout") != "keepout":
+        raise ValueError(f"unknown built-in constraint kind {cstr.get('kind')!r}: 'keepout' is the only one")
+    pos_idx = [int(k) for k in cstr["pos_idx"]]
+    centres, radius = xp.asarray(cstr["centres"]), xp.asarray(cstr["radius"]).reshape(-1)
+    K, pd = int(radius.shape[0]), len(pos_idx)
+    if pd not in (2, 3) or len(set(pos_idx)) != pd or min(pos_idx) < 0 or not 1 <= K <= 4:
+        raise ValueError("keep-out constraint: pos_idx holds 2 or 3 distinct state indices, and there are 1 to 4 balls")
+    if xdim is not None and max(pos_idx) >= xdim:
+        raise ValueError(f"keep-out constraint: pos_idx {pos_idx} outside the {xdim} states")
+    if tuple(centres.shape) not in ((K, pd), (N, K, pd), (M, N, K, pd)):
+        raise ValueError(f"keep-out constraint: centres must be ({K}, {pd}), ({N}, {K}, {pd}) or ({M}, {N}, {K}, {pd}), got {tuple(centres.shape)}")
+    if not bool((radius > 0).all()):
+        raise ValueError("keep-out constraint: every radius must be positive")
+    return pos_idx, centres.reshape((1,) * (4 - centres.ndim) + tuple(centres.shape)), radius
+
+
+def keepout_rows(X_prev, cstr):
+    """The convexification of the keep-out constraint about X_prev (M, N, x): `(a_x (M, N, K, x), h (M, N, K))`, row  a_x'X[i, j] <= h  with
+    a_x[pos_idx] = -n, h = -r - n'c, n = (pbar - c) / |pbar - c| the direction from the ball's centre to pbar = X_prev[i, j, pos_idx] (the
+    first position axis if |pbar - c| < 1e-12).  n'(p - c) >= r implies |p - c| >= r: every row's feasible set lies outside its ball."""
+    X_prev = np.asarray(X_prev, float)
+    M, N, x = X_prev.shape
+    pos_idx, cen, rad = _keepout_arrays(cstr, M, N, x)
+    cen = np.broadcast_to(np.asarray(cen, float), (M, N, rad.shape[0], len(pos_idx)))
+    d = X_prev[:, :, None, pos_idx] - cen
+    nrm = np.sqrt(np.sum(d * d, -1, keepdims=True))
+    deg = nrm < KEEPOUT_DEGENERATE
+    n = np.where(deg, np.eye(len(pos_idx))[0], d / np.where(deg, 1.0, nrm))
+    a_x = np.zeros((M, N, rad.shape[0], x))
+    a_x[..., pos_idx] = -n
+    return a_x, -np.asarray(rad, float) - np.sum(n * cen, -1)
+
+
+def keepout_augment(cstr, x0, f, fx, fu, X_prev, X_ref, Q, reg_x, x_l=None, x_u=None):
+    """`aux_state_problem` for "the K keep-out rows (form 0) on every (particle, stage)", dense and batched (py layout in and out): the state
+    grows to xd = x + K, component x + k of f~ is a_x'f, its row of fx~ / fu~ is a_x'fx / a_x'fu, the auxiliary block of Q~ is -reg_x, the
+    auxiliary entries of X_prev~, X_ref~, x0~ are 0, their bounds (-inf, h); the first x bounds are the caller's boxes (-+inf if none).
+    Returns dict(x0, f, fx, fu, X_prev, Q, X_ref, x_l, x_u, m=K) as `aux_state_problem` does."""
+    f, fx, fu = np.asarray(f, float), np.asarray(fx, float), np.asarray(fu, float)
+    M, N, x = f.shape
+    u = fu.shape[-1]
+    a_x, h = keepout_rows(X_prev, cstr)
+    K = h.shape[-1]
+    xd = x + K
+    F = np.zeros((M, N, xd)); F[..., :x] = f
+    F[..., x:] = np.einsum("mnkx,mnx->mnk", a_x, f)
+    FX = np.zeros((M, N, xd, xd)); FX[..., :x, :x] = fx
+    FX[..., x:, :x] = np.einsum("mnkx,mnxc->mnkc", a_x, fx)
+    FU = np.zeros((M, N, xd, u)); FU[..., :x, :] = fu
+    FU[..., x:, :] = np.einsum("mnkx,mnxc->mnkc", a_x, fu)
+    XP = np.zeros((M, N, xd)); XP[..., :x] = X_prev
+    XR = np.zeros((M, N, xd)); XR[..., :x] = X_ref
+    QQ = np.zeros((M, N, xd, xd)); QQ[..., :x, :x] = Q
+    QQ[..., np.arange(x, xd), np.arange(x, xd)] = -float(reg_x)
+    X0 = np.zeros((M, xd)); X0[:, :x] = x0
+    lo = np.full((M, N, xd), -np.inf); hi = np.full((M, N, xd), np.inf)
+    if x_l is not None and np.size(x_l):
+        lo[..., :x] = np.broadcast_to(x_l, (M, N, x))
+    if x_u is not None and np.size(x_u):
+        hi[..., :x] = np.broadcast_to(x_u, (M, N, x))
+    lo[np.isnan(lo)], hi[np.isnan(hi)] = -np.inf, np.inf
+    hi[..., x:] = h
+    return dict(x0=X0, f=F, fx=FX, fu=FU, X_prev=XP, Q=QQ, X_ref=XR, x_l=lo, x_u=hi, m=K)
+
+
+def make_keepout_extra_cstrs_fn(cstr, Nc=-1):
+    """An `extra_cstrs_fns(X_prev, U_prev, problems)` callable of the keep-out constraint for the host loop (and for upstream pmpc): one
+    reference-format tuple `(l, [], 0, G_left, ...)` with the M N K rows of `keepout_rows`, ordered (particle, stage, ball), over
+    z = [U_cons; U_free; X].  `Nc`: the `solver_settings["Nc"]` of the solve — the number of shared control stages decides where the
+    state columns of z begin (-1, the reference's default: every stage shared)."""
+
+    def extra_cstrs_fn(X_prev, U_prev, problems=None):
+        X_prev = np.asarray(X_prev, float)
+        single = X_prev.ndim == 2
+        Xp = X_prev[None] if single else X_prev
+        M, N, x = Xp.shape
+        u = np.asarray(U_prev).shape[-1]
+        Ncc = N if Nc < 0 else min(int(Nc), N)
+        ncu = Ncc * u + M * (N - Ncc) * u
+        n = ncu + M * N * x
+        a_x, h = keepout_rows(Xp, cstr)
+        K = h.shape[-1]
+        pos_idx = [int(k) for k in cstr["pos_idx"]]
+        l = M * N * K
+        unit = np.repeat(np.arange(M * N), K)  # row r = (i N + j) K + k
+        rows = np.repeat(np.arange(l), len(pos_idx))
+        cols = (ncu + unit * x)[:, None] + np.asarray(pos_idx)[None, :]
+        vals = a_x.reshape(l, x)[:, pos_idx]
+        G = sp.csr_matrix((vals.reshape(-1), (rows, cols.reshape(-1))), shape=(l, n))
+        return [(l, [], 0, G, sp.csr_matrix((l, 0)), h.reshape(-1).copy(), np.zeros(n), np.zeros(0))]
+
+    return extra_cstrs_fn

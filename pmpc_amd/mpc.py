@@ -40,6 +40,9 @@ class MPCController:
                  solver: Optional[DeviceSolver] = None, **unsupported):
         if builtin_model is None:
             raise ValueError("MPCController needs builtin_model=: a Python f_fx_fu_fn cannot enter the library's SCP loop")
+        if unsupported.get("builtin_cstr") is not None:
+            raise ValueError("MPCController: builtin_cstr is not supported (the library's SCP loop has one fixed state dimension; "
+                             "pmpc_amd.solve(..., device=..., builtin_cstr=...) carries the keep-out constraint)")
         bad = [k for k, v in unsupported.items() if v is not None and v != ""]
         if bad:
             raise ValueError(f"MPCController does not support {sorted(bad)}; the host loop pmpc_amd.solve(...) has the host-only features")

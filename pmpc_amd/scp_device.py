@@ -20,6 +20,13 @@ kernel; `Q` / `R` must be symmetric), while the `obj` column keeps the caller's 
 `builtin_cost=dict(kind="obstacles", pos_idx=..., centres=..., sigma=..., w=...)` is the built-in obstacle cost
 (`pmpc_amd.dynamics.obstacle_cost`), evaluated and applied in one launch.
 
+`builtin_cstr=dict(kind="keepout", pos_idx=..., centres=..., radius=...)` is the built-in keep-out constraint: every stage of every
+particle stays outside 1 to 4 balls in the position sub-space `pos_idx` (centres `(K, pos_dim)`, `(N, K, pos_dim)` moving, or
+`(M, N, K, pos_dim)` per particle).  Every iteration convexifies it about X_prev into half-spaces (`pmpc_amd.extra_cstrs.keepout_rows`)
+and restates them as upper bounds on K auxiliary states (`DeviceSolver.keepout_augment`, a HIP kernel): the sub-problem runs at
+`xdim + K` states, the loop sees `xdim`.  The host loop's equivalent is `extra_cstrs_fns=make_keepout_extra_cstrs_fn(...)`.  Refused
+next to it: a stage cone (`soc=` / `extra_cstrs`), slew penalties, `smooth_cstr="squareplus"`, a sharded context, fp32 Jacobians.
+
 Host-only features of the reference loop that need the sub-problem on the host (`extra_cstrs_fns`, filters, `solver_state`) are
 not offered here; `pmpc_amd.scp_mpc.scp_solve` (the default) has them.
 """
@@ -46,6 +53,23 @@ def _solver_for(device: torch.device) -> DeviceSolver:
     return _solvers[idx]
 
 
+def _refuse_with_cstr(settings=None, soc=None, slew_rate=None, u0_slew=None, solver=None, jac_dtype=None):
+    """The combinations `builtin_cstr` is refused in, each with its reason.  The first three are the cases `backend.aff_solve` refuses for
+    rows on the states (the keep-out rows are such rows), for the same reasons."""
+    settings = settings or {}
+    if soc is not None or settings.get("extra_cstrs"):
+        raise ValueError("builtin_cstr: rows on the states together with cones on the controls (soc= / extra_cstrs) are not supported in one solve")
+    if (slew_rate is not None and float(slew_rate) != 0.0) or u0_slew is not None or "slew_reg" in settings:
+        raise ValueError("builtin_cstr: rows on the states are not supported together with slew penalties")
+    if str(settings.get("smooth_cstr", "")).lower() == "squareplus":
+        raise ValueError('builtin_cstr: rows on the states together with smooth_cstr="squareplus" are not supported (the reference keeps '
+                         "extra_cstrs rows hard there; restated as state boxes they would be softened with the boxes)")
+    if solver is not None and getattr(solver, "world", 1) > 1:
+        raise ValueError("builtin_cstr: a sharded context (comm_world > 1) is not supported")
+    if jac_dtype is not None and jac_dtype != torch.float64:
+        raise ValueError(f"builtin_cstr: fp32 storage of the Jacobians ({jac_dtype}) is not supported (the augmentation kernel is fp64)")
+
+
 def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref=None, X_prev=None, U_prev=None, x_l=None,
                      x_u=None, u_l=None, u_u=None, verbose: bool = False, max_it: int = 100, time_limit: float = 1000.0,
                      res_tol: float = 1e-5, reg_x: float = 1e0, reg_u: float = 1e-2, slew_rate: Optional[float] = None,
@@ -54,12 +78,14 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
                      return_torch: bool = False, solver: Optional[DeviceSolver] = None, soc: Optional[Dict[str, Any]] = None,
                      lin_cost_fn=None, builtin_cost: Optional[Dict[str, Any]] = None, cost_fn=None,
                      extra_cstrs_fns=None, solver_state=None, filter_method: str = "", debug: bool = False,
-                     return_min_viol: bool = False, **ignored):
+                     return_min_viol: bool = False, builtin_cstr: Optional[Dict[str, Any]] = None, **ignored):
     host_only = dict(cost_fn=cost_fn, extra_cstrs_fns=extra_cstrs_fns, solver_state=solver_state,
                      filter_method=filter_method or None, debug=debug or None, return_min_viol=return_min_viol or None)
     bad = [k for k, v in host_only.items() if v is not None]
     if bad:
         raise ValueError(f"scp_solve(device=...) does not support {bad}; use the host loop (device=None)")
+    if builtin_cstr is not None:
+        _refuse_with_cstr(solver_settings, soc, slew_rate, u0_slew, solver)
     dev = torch.device(device)
     t_start = time.time()
     T = lambda z: None if z is None else torch.as_tensor(np.asarray(z) if not torch.is_tensor(z) else z, dtype=torch.float64, device=dev)
@@ -125,6 +151,25 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
     with_costs = lin_cost_fn is not None or builtin_cost is not None
     # the built-in cost's descriptor and device arrays: made once, before the loop (nothing of it is uploaded inside)
     cost_handle = s.prepare_cost(builtin_cost, N, xdim, dev) if builtin_cost is not None else None
+    # the built-in constraint: descriptor, the augmented buffers and the parts of the augmented problem that do not change with the
+    # iterate (Q~, x0~, the lower bounds, the first xdim upper bounds) — made once, before the loop
+    if builtin_cstr is not None:
+        _refuse_with_cstr(solver=s)
+        cstr_handle = s.prepare_cstr(builtin_cstr, M, N, xdim, dev)
+        Kc = cstr_handle[0].K
+        xd = xdim + Kc
+        mk = lambda *shape, fill=None: torch.empty(shape, dtype=torch.float64, device=dev) if fill is None else torch.full(shape, fill, dtype=torch.float64, device=dev)
+        aug = dict(f=mk(M, N, xd), fx=mk(M, N, xd, xd), fu=mk(M, N, udim, xd), X_prev=mk(M, N, xd), X_ref=mk(M, N, xd), xu=mk(M, N, xd, fill=math.inf))
+        lx_aug = mk(M, N, xd, fill=-math.inf)
+        if lx is not None:  # (NaN: "no bound" at the ABI, as aux_state_problem reads it)
+            lx_aug[..., :xdim] = torch.where(torch.isnan(lx), torch.full_like(lx, -math.inf), lx)
+            aug["xu"][..., :xdim] = torch.where(torch.isnan(ux), torch.full_like(ux, math.inf), ux)
+        Qa_aug = mk(M, N, xd, xd, fill=0.0)
+        Qa_aug[..., :xdim, :xdim] = Qa
+        Qa_aug[..., torch.arange(xdim, xd), torch.arange(xdim, xd)] = -float(reg_x)  # cancels the proximal term on the auxiliary states exactly
+        x0_aug = mk(M, xd, fill=0.0)
+        x0_aug[:, :xdim] = x0c
+        Xs_aug = mk(M, N, xd)
     it, max_res = 0, math.inf
     s.stream.wait_stream(torch.cuda.current_stream(dev))  # the set-up above ran on the caller's stream
     while it < max_it:
@@ -157,6 +202,14 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
                   X_out=Xs, U_out=Us, symmetric_cost=sym, verbose=bool(settings.get("verbose", False)),
                   static_cons_bounds=it > 0,  # the boxes are the same in every iteration of this loop (scp_mpc.py:338-376)
                   prev_is_last_solution=it > 0)  # and X_prev, U_prev are the previous iteration's X, U (scp_mpc.py:430)
+        if builtin_cstr is not None:
+            _refuse_with_cstr(jac_dtype=fxa.dtype)
+            # the keep-out rows about X_prev as bounds on K auxiliary states; the solve runs at xdim + K states.  prev_is_last_solution
+            # stays off: X_prev~ holds zeros where the previous output holds the rows' values, so the flag's promise (X_prev is the
+            # previous solve's output) does not hold for the augmented arrays
+            s.keepout_augment(cstr_handle, X_prev, f, fxa, fua, X_ref=X_ref_, out=aug)
+            kw.update(f=aug["f"], fx=aug["fx"], fu=aug["fu"], X_prev=aug["X_prev"], X_ref=aug["X_ref"], Q=Qa_aug, x0=x0_aug, lx=lx_aug,
+                      ux=aug["xu"], X_out=Xs_aug, prev_is_last_solution=False)
         if soc is not None:
             _, _, status = s.lsoc_solve(**soc_kw, **kw)
         elif cone:
@@ -164,6 +217,8 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
         else:
             _, _, status = s.lqp_solve(**kw)
         with torch.cuda.stream(s.stream):  # residual / objective row of scp_mpc.py:397-405 on the solver's stream
+            if builtin_cstr is not None:
+                Xs.copy_(Xs_aug[..., :xdim])  # strip the auxiliary states
             res = s.scp_residual(Xs, X_prev, Us, U_prev)[0]
             eX, eU = Xs - X_ref, Us - U_ref
             obj = (torch.sum(eX * torch.einsum("mnrt,mnt->mnr", Q, eX)) + torch.sum(eU * torch.einsum("mnrt,mnt->mnr", R, eU))) / N / M
