@@ -323,6 +323,19 @@ int pmpc_jac_live_mask(int model, unsigned char *fx_mask, unsigned char *fu_mask
  * Returns 1 if the variant is compiled for (xdim, udim), 0 if not, -1 if the pair has no active-set sweeps. */
 int pmpc_as_sweep_variant(int sweep, int xdim, int udim, int M, int Nc, unsigned flags, const int *knobs, int *out);
 
+/* How often each variant of a sweep has been launched by this process (every context and dims pair together) since it started or
+ * since the last call with reset != 0 — host-side counts of the launcher, for tests that must know which instantiations a solve ran
+ * (tests/test_as_variants_gpu.py).  The count of a variant stands at the code of its record:
+ *   sweep 0 (factor sweep, 72 codes):  mode + 3 * (skip + 2 * (defect + 2 * (ex + 3 * f32)))
+ *   sweep 1 (forward sweep, 32 codes): defect + 2 * pf2 + 4 * cone + 8 * f32 + 16 * sens
+ * Writes the first min(n, codes) counts to out (may be NULL), zeroes all counts if reset != 0, returns the number of codes (-1 for
+ * an unknown sweep).  A launch is counted when it is enqueued: rounds are enqueued ahead and a sweep that finds the device-side
+ * `done` flag set returns at once, so a count says that the instantiation ran, not that it had work to do.
+ * pmpc_as_sweep_knobs: out[0..2] = {deep2_maxm, deep_maxm, fwd_pf2_maxm} as this process's launchers read them (PMPC_AS_DEEP2_MAXM,
+ * PMPC_AS_DEEP_MAXM, PMPC_AS_FWD_PF2_MAXM; read once per process, at the first launch or this call). */
+int pmpc_as_sweep_launches(int sweep, unsigned long long *out, int n, int reset);
+void pmpc_as_sweep_knobs(int *out);
+
 /* SCP residual of one iteration (pmpc/scp_mpc.py:397-403): *out (device, one double) = max over particles and stages of
  * ||X - X_prev||_2 and ||U - U_prev||_2 (inf if a trajectory holds a NaN); asynchronous on pmpc_stream(). */
 int pmpc_scp_residual_device(pmpc_ctx *ctx, size_t xdim, size_t udim, size_t N, size_t M, const double *X, const double *X_prev,

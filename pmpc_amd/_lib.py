@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "pmpc_scp_residual_device", "pmpc_profile_read_partial", "pmpc_profile_read_all", "pmpc_scp_loop_device", "pmpc_linearize_device_f32",
     "pmpc_set_option", "pmpc_get_option", "pmpc_abi_struct_sizes", "pmpc_lcone_solve_host_ex", "pmpc_restart_stats",
     "pmpc_linearize_compact_device", "pmpc_expand_jac_device", "pmpc_jac_compact_doubles", "pmpc_jac_live_mask",
-    "pmpc_as_sweep_variant",
+    "pmpc_as_sweep_variant", "pmpc_as_sweep_launches", "pmpc_as_sweep_knobs",
     "pmpc_ref_shift_device", "pmpc_ref_shift_bad_pivots", "pmpc_obstacle_cost_grad_device", "pmpc_obstacle_ref_shift_device",
     "pmpc_scp_loop_device_cost", "pmpc_abi_scp_cost_size",
     "pmpc_rollout_device", "pmpc_shift_plan_device",
@@ -134,6 +134,11 @@ def load():
     if hasattr(lib, "pmpc_as_sweep_variant"):  # (likewise)
         lib.pmpc_as_sweep_variant.argtypes = [ctypes.c_int] * 5 + [ctypes.c_uint, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
         lib.pmpc_as_sweep_variant.restype = ctypes.c_int
+    if hasattr(lib, "pmpc_as_sweep_launches"):  # (likewise)
+        lib.pmpc_as_sweep_launches.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int, ctypes.c_int]
+        lib.pmpc_as_sweep_launches.restype = ctypes.c_int
+        lib.pmpc_as_sweep_knobs.argtypes = [ctypes.POINTER(ctypes.c_int)]
+        lib.pmpc_as_sweep_knobs.restype = None
     lib.pmpc_scp_residual_device.argtypes = [vp, sz, sz, sz, sz] + [vp] * 5
     lib.pmpc_scp_residual_device.restype = ctypes.c_int
     lib.pmpc_profile_enable.argtypes = [vp, ctypes.c_int]
@@ -222,6 +227,33 @@ def as_sweep_variant(sweep: str, x: int, u: int, M: int, Nc: int, flags: int, kn
     if got < 0:
         raise ValueError(f"({x}, {u}) is not a compiled pair of the active-set sweeps")
     return tuple(out[:5]), bool(got), tuple(bool(v) for v in out[5:8])
+
+
+def as_sweep_code(sweep: str, variant) -> int:
+    """Where pmpc_as_sweep_launches keeps the count of a variant record (the tuple as_sweep_variant returns): the layout that
+    include/pmpc_abi.h states."""
+    a, b, c, d, e = (int(v) for v in variant)
+    if sweep == "bwd":  # (mode, skip, defect, ex, f32)
+        return a + 3 * (b + 2 * (c + 2 * (d + 3 * e)))
+    return a + 2 * b + 4 * c + 8 * d + 16 * e  # (defect, pf2, cone, f32, sens)
+
+
+def as_sweep_launches(sweep: str, reset: bool = False):
+    """Launch counts of this process's active-set factor ("bwd") / forward ("fwd") sweeps per variant, indexed by as_sweep_code;
+    reset: start counting afresh.  Counts launches, not work: a sweep enqueued behind the round that finished the solve returns at once."""
+    lib = load()
+    sw = {"bwd": 0, "fwd": 1}[sweep]
+    n = lib.pmpc_as_sweep_launches(sw, None, 0, 0)
+    out = (ctypes.c_ulonglong * n)()
+    lib.pmpc_as_sweep_launches(sw, out, n, int(reset))
+    return [int(v) for v in out]
+
+
+def as_sweep_knobs():
+    """(deep2_maxm, deep_maxm, fwd_pf2_maxm) as the launchers of this process read them from the environment (once)."""
+    out = (ctypes.c_int * 3)()
+    load().pmpc_as_sweep_knobs(out)
+    return tuple(out)
 
 
 def dptr(a: np.ndarray):

@@ -29,6 +29,11 @@ constexpr BwdAsVariant select_bwd_as(int M, bool defect, bool settled_in, bool m
   return v;
 }
 
+// Index of a variant in the launch counts (pmpc_as_sweep_launches, include/pmpc_abi.h states the layout): one code per record
+constexpr int AS_BWD_CODES = 72, AS_FWD_CODES = 32;
+constexpr int bwd_as_code(const BwdAsVariant &v) { return v.mode + 3 * (v.skip + 2 * (v.defect + 2 * (v.ex + 3 * v.f32))); }
+constexpr int fwd_as_code(const FwdAsVariant &v) { return v.defect + 2 * v.pf2 + 4 * v.cone + 8 * v.f32 + 16 * v.sens; }
+
 // cone + SENS + DEFECT is the one forward sweep on the one-stage ring, whatever the knob says (registers)
 constexpr bool fwd_as_one_stage_only(bool defect, bool cone, bool sens) { return defect && cone && sens; }
 

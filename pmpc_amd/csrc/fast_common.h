@@ -187,7 +187,8 @@ __device__ __forceinline__ void chol_solve(const double (&Lc)[UD][UD], const dou
 }  // namespace
 
 // (xdim, udim) pairs with compiled instances (PMPC_DIAG_DIMS_12_4: diagnostic / A-B builds of the quadrotor shape only — the full
-// list takes minutes per file)
+// list takes minutes per file).  tests/support/as_variants.py keeps the full list as PAIRS (tests/test_as_variant.py compares the two):
+// tests/test_as_variants_gpu.py runs every variant of the active-set sweeps on every pair of it.
 #ifdef PMPC_DIAG_DIMS_12_4
 #define PMPC_FAST_DIMS(X) X(12, 4)
 #else

@@ -18,6 +18,7 @@
 //     back, the device decides (k_as_ctl) whether the later ones still have work.
 //
 // Reference semantics: the QP of PMPC.jl/src/lqp_utils.jl:2-393 restricted to an active set (same Newton system as kernels_fast.hip).
+#include <atomic>
 #include <type_traits>
 
 #include "fast_common.h"
@@ -1046,6 +1047,8 @@ const AsSweepKnobs &as_sweep_knobs() {  // read once per process
                                  getenv("PMPC_AS_FWD_PF2_MAXM") ? atoi(getenv("PMPC_AS_FWD_PF2_MAXM")) : (1 << 30)};
   return k;
 }
+// launches per variant since the process started (or the last reset), all pairs and contexts together: pmpc_as_sweep_launches
+std::atomic<unsigned long long> as_bwd_launches[AS_BWD_CODES], as_fwd_launches[AS_FWD_CODES];
 
 // The selected variant's fields become template arguments; only what as_variant.h lists as compiled is instantiated.
 template <int XD, int UD>
@@ -1055,6 +1058,7 @@ void launch_bwd_as_t(const LQArgs &a, hipStream_t s) {
   lift3(v.mode, [&](auto MODE) { lift(v.skip, [&](auto SKIP) { lift(v.defect, [&](auto DEFECT) { lift3(v.ex, [&](auto EX) { lift(v.f32, [&](auto F32) {
     if constexpr (bwd_as_compiled(BwdAsVariant{MODE, SKIP, DEFECT, EX, F32}, XD, UD)) {
       hipLaunchKernelGGL((k_bwd_as<XD, UD, MODE, SKIP, DEFECT, EX, std::conditional_t<F32, float, double>>), dim3(a.M), dim3(64), 0, s, a);
+      as_bwd_launches[bwd_as_code(v)].fetch_add(1, std::memory_order_relaxed);
       launched = true;
     }
   }); }); }); }); });
@@ -1067,6 +1071,7 @@ void launch_fwd_as_t(const LQArgs &a, hipStream_t s) {
   lift(v.defect, [&](auto DEFECT) { lift(v.pf2, [&](auto PF2) { lift(v.cone, [&](auto CONE) { lift(v.f32, [&](auto F32) { lift(v.sens, [&](auto SENS) {
     if constexpr (fwd_as_compiled(FwdAsVariant{DEFECT, PF2, CONE, F32, SENS}, XD, UD)) {
       hipLaunchKernelGGL((k_fwd_as<XD, UD, DEFECT, PF2, CONE, std::conditional_t<F32, float, double>, SENS>), dim3(a.M), dim3(64), 0, s, a);
+      as_fwd_launches[fwd_as_code(v)].fetch_add(1, std::memory_order_relaxed);
       launched = true;
     }
   }); }); }); }); });
@@ -1103,6 +1108,20 @@ int pmpc_as_sweep_variant(int sweep, int xdim, int udim, int M, int Nc, unsigned
   const FwdAsVariant v = select_fwd_as(M, Nc, defect, mat32, as_uraw, as_T, k);
   out[0] = v.defect; out[1] = v.pf2; out[2] = v.cone; out[3] = v.f32; out[4] = v.sens;
   return fwd_as_compiled(v, xdim, udim);
+}
+int pmpc_as_sweep_launches(int sweep, unsigned long long *out, int n, int reset) {
+  if (sweep != 0 && sweep != 1) return -1;
+  std::atomic<unsigned long long> *t = sweep == 0 ? as_bwd_launches : as_fwd_launches;
+  const int codes = sweep == 0 ? AS_BWD_CODES : AS_FWD_CODES;
+  for (int c = 0; c < codes; c++) {
+    const unsigned long long v = reset ? t[c].exchange(0, std::memory_order_relaxed) : t[c].load(std::memory_order_relaxed);
+    if (out && c < n) out[c] = v;
+  }
+  return codes;
+}
+void pmpc_as_sweep_knobs(int *out) {
+  const AsSweepKnobs &k = as_sweep_knobs();
+  out[0] = k.deep2_maxm; out[1] = k.deep_maxm; out[2] = k.fwd_pf2_maxm;
 }
 void launch_bwd_as(const LQArgs &a, hipStream_t s) {
 #define X(xd, ud) if (a.x == xd && a.u == ud) { launch_bwd_as_t<xd, ud>(a, s); return; }
