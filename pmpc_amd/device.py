@@ -23,6 +23,16 @@ def _p(t: Optional[torch.Tensor], dtype=torch.float64):
     return ctypes.c_void_p(t.data_ptr())
 
 
+class _TorchF64:
+    """The `xp` the array helpers of dynamics.py / extra_cstrs.py take (they call `xp.asarray` only): float64 tensors on `device`."""
+
+    def __init__(self, device):
+        self.device = device
+
+    def asarray(self, a):
+        return torch.as_tensor(a, dtype=torch.float64, device=self.device)
+
+
 class DeviceSolver:
     """Owns a pmpc_ctx (HIP stream + workspace cache + optional RCCL communicator)."""
 
@@ -154,29 +164,28 @@ class DeviceSolver:
             prob.cone_A, prob.cone_c, prob.cone_per_stage = _p(A), _p(cvec), int(per_stage)
         return prob, X_out, U_out
 
+    def _solve(self, entry, kw, verbose, wait_current_stream, *args):
+        """The part the three sub-problem solves share: the problem struct, one call of `entry` (`args` go between the problem and the
+        info struct) inside the stream contract, `last_info`."""
+        prob, X_out, U_out = self._problem(**kw)
+        info = _lib.PmpcInfo()
+        self._before(wait_current_stream)
+        status = entry(self.h, ctypes.byref(prob), *args, ctypes.byref(info), int(verbose))
+        self.last_info = {k: getattr(info, k) for k, _ in _lib.PmpcInfo._fields_}
+        self._after(wait_current_stream)
+        return X_out, U_out, status
+
     def lqp_solve(self, *, verbose=False, wait_current_stream=True, **kw):
         """All tensors float64 CUDA, ABI layout: vectors (M,N,d); matrices (M,N,col,row) i.e. the
         transpose of the py layout.  Returns X (M,N,x), U (M,N,u) (steps 1..N, no x0).  `weights` (M,): per-particle
         cost weights (the reference's `weights` setting, PMPC.jl/src/main.jl:96-112)."""
-        prob, X_out, U_out = self._problem(**kw)
-        info = _lib.PmpcInfo()
-        self._before(wait_current_stream)
-        status = self.lib.pmpc_lqp_solve_device(self.h, ctypes.byref(prob), ctypes.byref(info), int(verbose))
-        self.last_info = {k: getattr(info, k) for k, _ in _lib.PmpcInfo._fields_}
-        self._after(wait_current_stream)
-        return X_out, U_out, status
+        return self._solve(self.lib.pmpc_lqp_solve_device, kw, verbose, wait_current_stream)
 
     def lcone_solve(self, *, smooth_alpha=float("nan"), verbose=False, wait_current_stream=True, **kw):
         """The cone-path objective of `c_lcone_solve` (epsilon-anchored epigraph, PMPC.jl/src/main.jl:194-354) with
         every buffer in HBM; same tensor conventions as `lqp_solve`.  `cone_k` = the reference's `k` setting (worst-k
         objective for k < M; not reachable through its C ABI)."""
-        prob, X_out, U_out = self._problem(**kw)
-        info = _lib.PmpcInfo()
-        self._before(wait_current_stream)
-        status = self.lib.pmpc_lcone_solve_device(self.h, ctypes.byref(prob), float(smooth_alpha), ctypes.byref(info), int(verbose))
-        self.last_info = {k: getattr(info, k) for k, _ in _lib.PmpcInfo._fields_}
-        self._after(wait_current_stream)
-        return X_out, U_out, status
+        return self._solve(self.lib.pmpc_lcone_solve_device, kw, verbose, wait_current_stream, float(smooth_alpha))
 
     def lsoc_solve(self, *, verbose=False, wait_current_stream=True, **kw):
         """`lqp_solve` plus one second-order cone ||W u + w0||_2 <= v'u + v0 on the controls of every (particle, stage) —
@@ -185,13 +194,7 @@ class DeviceSolver:
         pyjulia-only `extra_cstrs` (README.md:219-239).  General form: `cones=dict(sizes=[q_k, ...], A=..., c=...)` — several
         cones per stage, cone k with q_k + 1 rows of `s = A u + c` (q_k = 0: a linear row s >= 0; q_k >= 1: |s[1:]| <= s[0]),
         `A (rows, udim)` / `c (rows,)` shared by all stages or `A (M, N, rows, udim)` / `c (M, N, rows)` per stage; `weights` allowed."""
-        prob, X_out, U_out = self._problem(**kw)
-        info = _lib.PmpcInfo()
-        self._before(wait_current_stream)
-        status = self.lib.pmpc_lsoc_solve_device(self.h, ctypes.byref(prob), ctypes.byref(info), int(verbose))
-        self.last_info = {k: getattr(info, k) for k, _ in _lib.PmpcInfo._fields_}
-        self._after(wait_current_stream)
-        return X_out, U_out, status
+        return self._solve(self.lib.pmpc_lsoc_solve_device, kw, verbose, wait_current_stream)
 
     def particle_costs(self, X, U, **kw):
         """J_i(X, U) of PMPC.jl/src/qp_utils.jl:60-162 for every particle (device tensor, (M,))."""
@@ -332,10 +335,7 @@ class DeviceSolver:
             return cost
         from .dynamics import _obstacle_arrays
 
-        class _xp:
-            asarray = staticmethod(lambda a: torch.as_tensor(a, dtype=torch.float64, device=device))
-
-        pos_idx, cen, sigma, w = _obstacle_arrays(cost, N, _xp)
+        pos_idx, cen, sigma, w = _obstacle_arrays(cost, N, _TorchF64(device))
         if max(pos_idx) >= x or min(pos_idx) < 0:
             raise ValueError(f"obstacle cost: pos_idx {pos_idx} outside the {x} states")
         keep = [cen.contiguous(), sigma.contiguous(), w.contiguous()]
@@ -376,10 +376,7 @@ class DeviceSolver:
             return cstr
         from .extra_cstrs import _keepout_arrays
 
-        class _xp:
-            asarray = staticmethod(lambda a: torch.as_tensor(a, dtype=torch.float64, device=device))
-
-        pos_idx, cen, rad = _keepout_arrays(cstr, M, N, x, _xp)
+        pos_idx, cen, rad = _keepout_arrays(cstr, M, N, x, _TorchF64(device))
         K, pd = int(rad.shape[0]), len(pos_idx)
         if x + K > 16:
             raise ValueError(f"keep-out constraint: {x} states + {K} auxiliary states exceed the solver's 16")

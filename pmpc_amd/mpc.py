@@ -27,10 +27,10 @@ import numpy as np
 import torch
 
 from .device import DeviceSolver
+from .device_problem import build_problem
 from .dynamics import model_id
 
 _SETTINGS = ("solver", "Nc", "smooth_alpha", "slew_reg", "extra_cstrs", "soc_u_interior")
-_CONE_SOLVERS = ("ecos", "gurobi", "mosek", "cosmo")
 
 
 class MPCController:
@@ -55,12 +55,8 @@ class MPCController:
         self.model = model_id(builtin_model)
         dev = torch.device(device)
         self.device = dev
-        T = lambda z: torch.as_tensor(np.asarray(z) if not torch.is_tensor(z) else z, dtype=torch.float64, device=dev)
-        Q, R = T(Q), T(R)
-        if Q.ndim != 4 or R.ndim != 4:
+        if np.ndim(Q) != 4 or np.ndim(R) != 4:
             raise ValueError("MPCController: Q (M, N, x, x) and R (M, N, u, u)")
-        M, N, x, u = Q.shape[0], Q.shape[1], Q.shape[-1], R.shape[-1]
-        self.M, self.N, self.xdim, self.udim = M, N, x, u
         if solver is None:
             from .scp_device import _solver_for
 
@@ -68,52 +64,28 @@ class MPCController:
         if solver.world > 1:
             raise ValueError("MPCController: a sharded context (comm_world > 1) is not supported")
         self.solver = s = solver
-        vec = lambda z, d: T(z).reshape(M, N, d).contiguous().clone()
-        has = lambda z: z is not None and (z.numel() if torch.is_tensor(z) else np.size(z)) > 0
-        Qa, Ra = Q.transpose(-1, -2).contiguous(), R.transpose(-1, -2).contiguous()  # ABI: column-major blocks
-        sym = bool(torch.equal(Qa, Q) and torch.equal(Ra, R))
-        if builtin_cost is not None and not sym:
-            raise ValueError("builtin_cost needs symmetric Q and R blocks (the reference shift is a Cholesky solve with them)")
-        self.X_ref = torch.zeros((M, N, x), dtype=torch.float64, device=dev) if X_ref is None else vec(X_ref, x)
-        self.U_ref = torch.zeros((M, N, u), dtype=torch.float64, device=dev) if U_ref is None else vec(U_ref, u)
-        lx, ux = (vec(x_l, x), vec(x_u, x)) if has(x_l) and has(x_u) else (None, None)
-        lu, uu = (vec(u_l, u), vec(u_u, u)) if has(u_l) and has(u_u) else (None, None)
-        self.params = T(params).reshape(M, -1).contiguous().clone()
-        solver_name = str(settings.get("solver", "ecos")).lower()
-        cone = solver_name in _CONE_SOLVERS or "smooth_alpha" in settings
-        alpha = float(settings.get("smooth_alpha", math.nan))
-        Nc = int(settings.get("Nc", -1))
+        # the problem as the library takes it (device_problem.py), with copies of the references, boxes and params of its own:
+        # `set_reference` and `reset` write the references in place
+        p = build_problem(Q, R, None, X_ref, U_ref, None, None, x_l, x_u, u_l, u_u, reg_x, reg_u, slew_rate, u0_slew, settings, soc, builtin_model,
+                          params, dev, own_copies=True, need_sym="builtin_cost needs" if builtin_cost is not None else None)
+        M, N, x, u = p.M, p.N, p.xdim, p.udim
+        self.M, self.N, self.xdim, self.udim = M, N, x, u
+        self.X_ref, self.U_ref, self.params = p.X_ref, p.U_ref, p.params
         mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
-        slew = torch.full((M,), float(slew_rate), dtype=torch.float64, device=dev) if slew_rate is not None and float(slew_rate) != 0.0 else None
         # slew_reg: the penalty on U[0] - (the control applied last); that control is u0_slew before the first step (None: the first
         # step has no such term, as solve(..., u0_slew=None)) and the shift's um1' from then on
-        self._slew0 = torch.full((M,), float(settings["slew_reg"]), dtype=torch.float64, device=dev) if "slew_reg" in settings else None
+        self._slew0 = p.slew_reg0
         self._um1 = mk(M, u) if self._slew0 is not None else None
-        self._u0_slew = None if u0_slew is None or self._um1 is None else T(u0_slew).reshape(-1, u).expand(M, u).contiguous()
-        soc_kw = {}
-        if soc is None and settings.get("extra_cstrs"):  # the reference's tuple format, stage-wise SOC case only (as scp_device.py)
-            from .extra_cstrs import stage_soc_from_extra_cstrs
-
-            tuples = list(settings["extra_cstrs"])
-            if len(tuples) != 1:
-                raise ValueError("one extra_cstrs tuple (the stage-wise second-order cone) is supported")
-            soc = stage_soc_from_extra_cstrs(tuples[0], M, N, x, u, Nc)
-            if "soc_u_interior" not in settings:
-                raise ValueError("solver_settings['soc_u_interior'] (a control strictly inside the boxes and the cone) is required")
-            soc["u_interior"] = settings["soc_u_interior"]
-        if soc is not None:
-            soc_kw = dict(soc_W=T(soc["W"]).reshape(-1, u).contiguous(), soc_w0=T(soc["w0"]).reshape(-1).contiguous(),
-                          soc_v=T(soc["v"]).reshape(u).contiguous(), soc_v0=float(soc.get("v0", 0.0)),
-                          soc_u_interior=T(soc["u_interior"]).reshape(u).contiguous())
-        elif cone:  # as bench.py drives the cone objective through the loop (smoothing: barrier_mu = 1 / alpha)
-            soc_kw = dict(cone_objective=True, barrier_mu=0.0 if math.isnan(alpha) else 1.0 / alpha)
+        self._u0_slew = p.um1
+        soc_kw = p.soc_kw
+        if not soc_kw and p.cone:  # as bench.py drives the cone objective through the loop (smoothing: barrier_mu = 1 / alpha)
+            soc_kw = dict(cone_objective=True, barrier_mu=0.0 if math.isnan(p.smooth_alpha) else 1.0 / p.smooth_alpha)
         self._x0 = mk(M, x)
-        self._pairs = [(mk(M, N, x), mk(M, N, u)), (mk(M, N, x), mk(M, N, u))]  # the two trajectory pairs of the loop
+        self._pairs = [(p.X_prev, p.U_prev), (mk(M, N, x), mk(M, N, u))]  # the two trajectory pairs of the loop (`reset` fills the first)
         self._lin = [mk(M, N, x), mk(M, N, x, x), mk(M, N, u, x), mk(M, N, x), mk(M, N, x, x), mk(M, N, u, x)]  # f, fx, fu; f2, fx2, fu2
         self._res = mk(64)
         self._cost = s.prepare_cost(builtin_cost, N, x, dev) if builtin_cost is not None else None
-        self._kw = dict(Q=Qa, R=Ra, X_ref=self.X_ref, U_ref=self.U_ref, reg_x=float(reg_x), reg_u=float(reg_u), Nc=Nc, x0=self._x0, lx=lx, ux=ux,
-                        lu=lu, uu=uu, slew_reg=slew, symmetric_cost=sym, **soc_kw)
+        self._kw = dict(p.solve_kw(), x0=self._x0, X_ref=self.X_ref, U_ref=self.U_ref, **soc_kw)
         torch.cuda.current_stream(dev).synchronize()  # (the uploads above ran on the caller's stream; the kernels read them on the solver's)
         self.reset()
 

@@ -29,6 +29,8 @@ next to it: a stage cone (`soc=` / `extra_cstrs`), slew penalties, `smooth_cstr=
 
 Host-only features of the reference loop that need the sub-problem on the host (`extra_cstrs_fns`, filters, `solver_state`) are
 not offered here; `pmpc_amd.scp_mpc.scp_solve` (the default) has them.
+
+The arguments become a `DeviceProblem` (pmpc_amd/device_problem.py `build_problem`, shared with `MPCController`) before the loop.
 """
 from __future__ import annotations
 
@@ -36,13 +38,12 @@ import math
 import time
 from typing import Any, Callable, Dict, Optional
 
-import numpy as np
 import torch
 
-from .device import MODEL_BICYCLE, MODEL_QUADROTOR, MODEL_UNICYCLE, DeviceSolver
+from .device import DeviceSolver
+from .device_problem import build_problem, keepout_static
 from .utils import TablePrinter
 
-_MODELS = {"unicycle": MODEL_UNICYCLE, "quadrotor": MODEL_QUADROTOR, "bicycle": MODEL_BICYCLE}
 _solvers: Dict[int, DeviceSolver] = {}
 
 
@@ -88,67 +89,22 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
         _refuse_with_cstr(solver_settings, soc, slew_rate, u0_slew, solver)
     dev = torch.device(device)
     t_start = time.time()
-    T = lambda z: None if z is None else torch.as_tensor(np.asarray(z) if not torch.is_tensor(z) else z, dtype=torch.float64, device=dev)
-    Q, R, x0 = T(Q), T(R), T(x0)
-    single = x0.ndim == 1  # pmpc/scp_mpc.py:297-309
-    if single:
-        assert Q.ndim == 3 and R.ndim == 3
-        Q, R, x0 = Q[None], R[None], x0[None]
-    M, N, xdim, udim = Q.shape[0], Q.shape[1], Q.shape[-1], R.shape[-1]
-    vec = lambda z, d: None if z is None else T(z).reshape(M, N, d).contiguous()
-    X_ref = torch.zeros((M, N, xdim), dtype=torch.float64, device=dev) if X_ref is None else vec(X_ref, xdim)
-    U_ref = torch.zeros((M, N, udim), dtype=torch.float64, device=dev) if U_ref is None else vec(U_ref, udim)
-    X_prev = X_ref.clone() if X_prev is None else vec(X_prev, xdim).clone()  # default: X_ref (:313)
-    U_prev = U_ref.clone() if U_prev is None else vec(U_prev, udim).clone()
-    has = lambda z: z is not None and np.size(z) > 0
-    lx, ux = (vec(x_l, xdim), vec(x_u, xdim)) if has(x_l) and has(x_u) else (None, None)
-    lu, uu = (vec(u_l, udim), vec(u_u, udim)) if has(u_l) and has(u_u) else (None, None)
-    Qa, Ra = Q.transpose(-1, -2).contiguous(), R.transpose(-1, -2).contiguous()  # ABI: column-major blocks
-    sym = bool(torch.equal(Qa, Q) and torch.equal(Ra, R))
-    if (lin_cost_fn is not None or builtin_cost is not None) and not sym:
-        raise ValueError("lin_cost_fn / builtin_cost need symmetric Q and R blocks (the reference shift is a Cholesky solve with them)")
-    settings = dict(solver_settings or {})
-    solver_name = str(settings.get("solver", "ecos")).lower()  # static_backend.py:242-253
-    cone = solver_name in ("ecos", "gurobi", "mosek", "cosmo") or "smooth_cstr" in settings or "smooth_alpha" in settings
-    smooth_alpha = float(settings.get("smooth_alpha", math.nan))
-    Nc = int(settings.get("Nc", -1))
-    slew = None
-    if slew_rate is not None and float(slew_rate) != 0.0:
-        slew = torch.full((M,), float(slew_rate), dtype=torch.float64, device=dev)
-    slew0 = um1 = None
-    if "slew_reg" in settings and u0_slew is not None:  # static_backend.py:263-272
-        slew0 = torch.full((M,), float(settings["slew_reg"]), dtype=torch.float64, device=dev)
-        um1 = T(u0_slew).reshape(-1, udim).expand(M, udim).contiguous()
+    with_costs = lin_cost_fn is not None or builtin_cost is not None
+    p = build_problem(Q, R, x0, X_ref, U_ref, X_prev, U_prev, x_l, x_u, u_l, u_u, reg_x, reg_u, slew_rate, u0_slew, solver_settings, soc,
+                      builtin_model, params, dev, need_sym="lin_cost_fn / builtin_cost need" if with_costs else None)
+    M, N, xdim, udim, single = p.M, p.N, p.xdim, p.udim, p.single
+    X_prev, U_prev = p.X_prev, p.U_prev
+    T = lambda z: torch.as_tensor(z, dtype=torch.float64, device=dev)  # (lin_cost_fn's gradients)
     s = solver or _solver_for(dev)
-    model = _MODELS[builtin_model] if builtin_model is not None else None
-    if model is not None:
-        assert params is not None, "builtin_model needs `params` (M, 3) unicycle / (M, 4) quadrotor / (M, 2) bicycle"
-        params = T(params).reshape(M, -1).contiguous()
-    x0c = x0.contiguous()
-    soc_kw = {}
-    if soc is None and settings.get("extra_cstrs"):  # the reference's tuple format, stage-wise SOC case only
-        from .extra_cstrs import stage_soc_from_extra_cstrs
-
-        tuples = list(settings["extra_cstrs"])
-        if len(tuples) != 1:
-            raise ValueError("one extra_cstrs tuple (the stage-wise second-order cone) is supported")
-        soc = stage_soc_from_extra_cstrs(tuples[0], M, N, xdim, udim, Nc)
-        if "soc_u_interior" not in settings:
-            raise ValueError("solver_settings['soc_u_interior'] (a control strictly inside the boxes and the cone) is required")
-        soc["u_interior"] = settings["soc_u_interior"]
-    if soc is not None:
-        soc_kw = dict(soc_W=T(soc["W"]).reshape(-1, udim).contiguous(), soc_w0=T(soc["w0"]).reshape(-1).contiguous(),
-                      soc_v=T(soc["v"]).reshape(udim).contiguous(), soc_v0=float(soc.get("v0", 0.0)),
-                      soc_u_interior=T(soc["u_interior"]).reshape(udim).contiguous())
     Xs = torch.empty((M, N, xdim), dtype=torch.float64, device=dev)
     Us = torch.empty((M, N, udim), dtype=torch.float64, device=dev)
+    static_kw = dict(p.solve_kw(), slew_reg0=p.slew0, slew_um1=p.um1, X_out=Xs, U_out=Us, verbose=p.solver_verbose)
 
     data: Dict[str, Any] = dict(solver_data=[], hist=[], t_aff_solve=[])
     fields = ["it", "elaps", "obj", "resid", "reg_x", "reg_u"]
     tp = TablePrinter(fields, fmts=["%04d"] + ["%8.3e"] * 5)
     if verbose:
         print(tp.make_header())
-    with_costs = lin_cost_fn is not None or builtin_cost is not None
     # the built-in cost's descriptor and device arrays: made once, before the loop (nothing of it is uploaded inside)
     cost_handle = s.prepare_cost(builtin_cost, N, xdim, dev) if builtin_cost is not None else None
     # the built-in constraint: descriptor, the augmented buffers and the parts of the augmented problem that do not change with the
@@ -156,27 +112,18 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
     if builtin_cstr is not None:
         _refuse_with_cstr(solver=s)
         cstr_handle = s.prepare_cstr(builtin_cstr, M, N, xdim, dev)
-        Kc = cstr_handle[0].K
-        xd = xdim + Kc
-        mk = lambda *shape, fill=None: torch.empty(shape, dtype=torch.float64, device=dev) if fill is None else torch.full(shape, fill, dtype=torch.float64, device=dev)
-        aug = dict(f=mk(M, N, xd), fx=mk(M, N, xd, xd), fu=mk(M, N, udim, xd), X_prev=mk(M, N, xd), X_ref=mk(M, N, xd), xu=mk(M, N, xd, fill=math.inf))
-        lx_aug = mk(M, N, xd, fill=-math.inf)
-        if lx is not None:  # (NaN: "no bound" at the ABI, as aux_state_problem reads it)
-            lx_aug[..., :xdim] = torch.where(torch.isnan(lx), torch.full_like(lx, -math.inf), lx)
-            aug["xu"][..., :xdim] = torch.where(torch.isnan(ux), torch.full_like(ux, math.inf), ux)
-        Qa_aug = mk(M, N, xd, xd, fill=0.0)
-        Qa_aug[..., :xdim, :xdim] = Qa
-        Qa_aug[..., torch.arange(xdim, xd), torch.arange(xdim, xd)] = -float(reg_x)  # cancels the proximal term on the auxiliary states exactly
-        x0_aug = mk(M, xd, fill=0.0)
-        x0_aug[:, :xdim] = x0c
+        xd = xdim + cstr_handle[0].K
+        static = keepout_static(p, cstr_handle[0].K)
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        aug = dict(f=mk(M, N, xd), fx=mk(M, N, xd, xd), fu=mk(M, N, udim, xd), X_prev=mk(M, N, xd), X_ref=mk(M, N, xd), xu=static["xu"])
         Xs_aug = mk(M, N, xd)
     it, max_res = 0, math.inf
     s.stream.wait_stream(torch.cuda.current_stream(dev))  # the set-up above ran on the caller's stream
     while it < max_it:
-        if model is not None:
-            f, fxa, fua = s.linearize(model, x0c, X_prev, U_prev, params)
+        if p.model is not None:
+            f, fxa, fua = s.linearize(p.model, p.x0, X_prev, U_prev, p.params)
         else:
-            X_lin = torch.cat([x0[:, None, :], X_prev[:, :-1, :]], 1)
+            X_lin = torch.cat([p.x0[:, None, :], X_prev[:, :-1, :]], 1)
             f, fx, fu = f_fx_fu_fn(X_lin if not single else X_lin[0], U_prev if not single else U_prev[0])
             f = f.reshape(M, N, xdim).contiguous()
             if jacobians_abi_layout:
@@ -185,21 +132,19 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
                 fxa = fx.reshape(M, N, xdim, xdim).transpose(-1, -2).contiguous()
                 fua = fu.reshape(M, N, xdim, udim).transpose(-1, -2).contiguous()
         # linearised costs (scp_mpc.py:171-185, 352): this iteration's references; X_ref / U_ref stay as they are for the `obj` column
-        X_ref_, U_ref_ = X_ref, U_ref
+        X_ref_, U_ref_ = p.X_ref, p.U_ref
         if builtin_cost is not None:
-            X_ref_ = s.obstacle_cost_grad(X_prev, cost_handle, Q=Qa, X_ref=X_ref_, check=False)
+            X_ref_ = s.obstacle_cost_grad(X_prev, cost_handle, Q=p.Qa, X_ref=X_ref_, check=False)
         if lin_cost_fn is not None:
-            problems = dict(ignored, f=f, fx=fxa, fu=fua, x0=x0, X_prev=X_prev, U_prev=U_prev, Q=Q, R=R, X_ref=X_ref, U_ref=U_ref,
-                            x_l=lx, x_u=ux, u_l=lu, u_u=uu, slew_rate=slew_rate, u0_slew=u0_slew, jacobians_abi_layout=True)
+            problems = dict(ignored, f=f, fx=fxa, fu=fua, x0=p.x0, X_prev=X_prev, U_prev=U_prev, Q=p.Q, R=p.R, X_ref=p.X_ref, U_ref=p.U_ref,
+                            x_l=p.lx, x_u=p.ux, u_l=p.lu, u_u=p.uu, slew_rate=slew_rate, u0_slew=u0_slew, jacobians_abi_layout=True)
             cx, cu = lin_cost_fn(X_prev if not single else X_prev[0], U_prev if not single else U_prev[0], problems)
             if cx is not None:
-                X_ref_ = s.ref_shift(Qa, T(cx).reshape(M, N, xdim).contiguous(), X_ref_, check=False)
+                X_ref_ = s.ref_shift(p.Qa, T(cx).reshape(M, N, xdim).contiguous(), X_ref_, check=False)
             if cu is not None:
-                U_ref_ = s.ref_shift(Ra, T(cu).reshape(M, N, udim).contiguous(), U_ref, check=False)
+                U_ref_ = s.ref_shift(p.Ra, T(cu).reshape(M, N, udim).contiguous(), p.U_ref, check=False)
         t_aff = time.time()
-        kw = dict(f=f, fx=fxa, fu=fua, X_prev=X_prev, U_prev=U_prev, Q=Qa, R=Ra, X_ref=X_ref_, U_ref=U_ref_, reg_x=float(reg_x),
-                  reg_u=float(reg_u), Nc=Nc, x0=x0c, lx=lx, ux=ux, lu=lu, uu=uu, slew_reg=slew, slew_reg0=slew0, slew_um1=um1,
-                  X_out=Xs, U_out=Us, symmetric_cost=sym, verbose=bool(settings.get("verbose", False)),
+        kw = dict(static_kw, f=f, fx=fxa, fu=fua, X_prev=X_prev, U_prev=U_prev, X_ref=X_ref_, U_ref=U_ref_,
                   static_cons_bounds=it > 0,  # the boxes are the same in every iteration of this loop (scp_mpc.py:338-376)
                   prev_is_last_solution=it > 0)  # and X_prev, U_prev are the previous iteration's X, U (scp_mpc.py:430)
         if builtin_cstr is not None:
@@ -208,20 +153,20 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
             # stays off: X_prev~ holds zeros where the previous output holds the rows' values, so the flag's promise (X_prev is the
             # previous solve's output) does not hold for the augmented arrays
             s.keepout_augment(cstr_handle, X_prev, f, fxa, fua, X_ref=X_ref_, out=aug)
-            kw.update(f=aug["f"], fx=aug["fx"], fu=aug["fu"], X_prev=aug["X_prev"], X_ref=aug["X_ref"], Q=Qa_aug, x0=x0_aug, lx=lx_aug,
+            kw.update(f=aug["f"], fx=aug["fx"], fu=aug["fu"], X_prev=aug["X_prev"], X_ref=aug["X_ref"], Q=static["Qa"], x0=static["x0"], lx=static["lx"],
                       ux=aug["xu"], X_out=Xs_aug, prev_is_last_solution=False)
-        if soc is not None:
-            _, _, status = s.lsoc_solve(**soc_kw, **kw)
-        elif cone:
-            _, _, status = s.lcone_solve(smooth_alpha=smooth_alpha, **kw)
+        if p.soc_kw:
+            _, _, status = s.lsoc_solve(**p.soc_kw, **kw)
+        elif p.cone:
+            _, _, status = s.lcone_solve(smooth_alpha=p.smooth_alpha, **kw)
         else:
             _, _, status = s.lqp_solve(**kw)
         with torch.cuda.stream(s.stream):  # residual / objective row of scp_mpc.py:397-405 on the solver's stream
             if builtin_cstr is not None:
                 Xs.copy_(Xs_aug[..., :xdim])  # strip the auxiliary states
             res = s.scp_residual(Xs, X_prev, Us, U_prev)[0]
-            eX, eU = Xs - X_ref, Us - U_ref
-            obj = (torch.sum(eX * torch.einsum("mnrt,mnt->mnr", Q, eX)) + torch.sum(eU * torch.einsum("mnrt,mnt->mnr", R, eU))) / N / M
+            eX, eU = Xs - p.X_ref, Us - p.U_ref
+            obj = (torch.sum(eX * torch.einsum("mnrt,mnt->mnr", p.Q, eX)) + torch.sum(eU * torch.einsum("mnrt,mnt->mnr", p.R, eU))) / N / M
             row = torch.stack([res, obj]).cpu()  # the only device->host read of the iteration (synchronises the stream)
             X_prev, U_prev = Xs.clone(), Us.clone()
         torch.cuda.current_stream(dev).wait_stream(s.stream)
@@ -248,7 +193,7 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
         print(tp.make_footer())
     if with_costs:  # the shifts' device-side counter of refused blocks: read once, after the loop
         s.check_bad_pivots("lin_cost_fn / builtin_cost: Q or R")
-    X = torch.cat([x0[:, None, :], X_prev], 1)
+    X = torch.cat([p.x0[:, None, :], X_prev], 1)
     U = U_prev
     if single:
         X, U = X[0], U[0]
