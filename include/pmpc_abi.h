@@ -434,6 +434,45 @@ int pmpc_keepout_augment_device(pmpc_ctx *ctx, const pmpc_scp_cstr *cstr, size_t
                                 const double *X_prev, const double *f, const double *fx, const double *fu, const double *X_ref,
                                 double *f_aug, double *fx_aug, double *fu_aug, double *X_prev_aug, double *X_ref_aug, double *xu_aug);
 
+/* The way back from a sub-problem at xd = xdim + K states, one launch: X (M, N, xdim) <- the first xdim entries of every row of X_aug
+ * (M, N, xd), and *out (device) <- the SCP residual of (X, X_prev), (U, U_prev) exactly as pmpc_scp_residual_device gives it for the
+ * stripped array (the same sums in the same order; *out is zeroed first).  X_aug and X must not overlap.  Asynchronous on pmpc_stream().
+ * Returns 0; 2 and launches nothing for a null pointer, K outside 1 .. 4, xdim + K > 16, udim outside 1 .. 16, N == 0 or M == 0; 1 on a
+ * HIP error. */
+int pmpc_keepout_strip_residual_device(pmpc_ctx *ctx, size_t xdim, int K, size_t udim, size_t N, size_t M, const double *X_aug, double *X,
+                                       const double *X_prev, const double *U, const double *U_prev, double *out);
+
+/* The buffers of pmpc_scp_loop_device_cstr at xd = xdim + K states (device, caller-allocated once; the library allocates nothing per call
+ * and writes none of the static parts).  Static, the caller's: Q (M, N, xd, xd) = the problem's blocks with -reg_x on the auxiliary
+ * diagonal, x0 (M, xd) = [x0 | 0], lx (M, N, xd) = [lx or -inf | -inf], and the first xdim entries of every row of BOTH xu arrays
+ * (ux or +inf; no NaN).  Iterate-dependent, two sets used like the linearisation scratch sets (the augmentation enqueued behind a
+ * sub-problem's rounds writes the set the running solve does not read): f, X_prev, X_ref, xu (M, N, xd), fx (M, N, xd, xd),
+ * fu (M, N, udim, xd) — the loop writes all of them but the first xdim entries of xu's rows.  X_out (M, N, xd): the sub-problem's output. */
+typedef struct pmpc_scp_aug {
+  const double *Q, *x0, *lx;
+  double *f[2], *fx[2], *fu[2], *X_prev[2], *X_ref[2], *xu[2];
+  double *X_out;
+} pmpc_scp_aug;
+size_t pmpc_abi_scp_aug_size(void); /* sizeof(pmpc_scp_aug) as the library was built (see pmpc_abi_struct_sizes) */
+
+/* pmpc_scp_loop_device_cost with a built-in constraint (`cstr` NULL or kind 0: exactly pmpc_scp_loop_device_cost, launch for launch;
+ * `aug` is not read then).  With a keep-out constraint an iteration is: dense linearisation at xdim about (X_prev, U_prev) (no compact
+ * records) -> the cost's shift, if any -> pmpc_keepout_augment_device's launch into set `cur` of `aug` (its X_ref: this iteration's
+ * shifted reference) -> the sub-problem at xd states on aug's Q, x0, lx, xu[cur] with PMPC_PREV_IS_LAST_SOLUTION off in every iteration
+ * (X_prev~ holds zeros where the last output holds the rows' values), X_out = aug->X_out, U_out = the loop's -> strip + residual
+ * (pmpc_keepout_strip_residual_device's launch) -> swap.  The trajectory pairs, res, infos, *last_in_out and the return value are
+ * pmpc_scp_loop_device's, at xdim; on a HIP error aug->X_out is filled with NaN along with the pairs.  Behind a sub-problem's first
+ * batch of rounds the loop enqueues the strip, the residual, the next linearisation, its shift and its augmentation (into the other set);
+ * if the rounds did not suffice the strip and the residual are redone from the finished output.
+ * Refused before anything runs (0, infos[0].status = 2): an invalid description, xdim + K > 16, a null `aug` or a null pointer in it,
+ * a stage cone (soc_u_interior / cone_count), PMPC_HAS_SLEW / PMPC_HAS_SLEW0, PMPC_F32_MATRICES, a sharded context, smooth_cstr = 1. */
+int pmpc_scp_loop_device_cstr(pmpc_ctx *ctx, int model, const double *params, const pmpc_problem *p, double *f2, double *fx2,
+                              double *fu2, int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out,
+                              const pmpc_scp_cost *cost, const pmpc_scp_cstr *cstr, const pmpc_scp_aug *aug);
+/* Iterations of pmpc_scp_loop_device* in this process whose follow-up (residual, next linearisation) was taken as enqueued behind the
+ * sub-problem's first batch of rounds (out2[0]) / was enqueued after the solve had returned (out2[1]); reset: start counting afresh. */
+void pmpc_scp_loop_follow_ups(unsigned long long *out2, int reset);
+
 /* Live kernel timing for bench.py: HIP events on pmpc_stream() around the launches of a class
  * (0 backward+factor, 1 backward vector-only, 2 forward, 3 consensus reduce+solve).
  * level 0 = off, 1 = class 0 only (the dominant kernel; what bench.py's roofline needs), 2 = every class

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "pmpc_scp_loop_device_cost", "pmpc_abi_scp_cost_size",
     "pmpc_rollout_device", "pmpc_shift_plan_device",
     "pmpc_keepout_augment_device", "pmpc_abi_scp_cstr_size",
+    "pmpc_keepout_strip_residual_device", "pmpc_scp_loop_device_cstr", "pmpc_abi_scp_aug_size", "pmpc_scp_loop_follow_ups",
 ]
 
 
@@ -65,6 +66,12 @@ class PmpcScpCstr(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int), ("K", ctypes.c_int), ("pos_dim", ctypes.c_int), ("pos_idx", ctypes.c_int * 3),
                 ("centre_stride_particle", ctypes.c_longlong), ("centre_stride_stage", ctypes.c_longlong),
                 ("centres", ctypes.c_void_p), ("radius", ctypes.c_void_p)]
+
+
+class PmpcScpAug(ctypes.Structure):
+    """pmpc_scp_aug (include/pmpc_abi.h): the augmented buffers of pmpc_scp_loop_device_cstr."""
+    _fields_ = ([(k, ctypes.c_void_p) for k in ("Q", "x0", "lx")] + [(k, ctypes.c_void_p * 2) for k in ("f", "fx", "fu", "X_prev", "X_ref", "xu")]
+                + [("X_out", ctypes.c_void_p)])
 
 
 def load():
@@ -183,6 +190,18 @@ def load():
         if lib.pmpc_abi_scp_cstr_size() != ctypes.sizeof(PmpcScpCstr):
             raise ImportError(f"{LIB_PATH} and pmpc_amd/_lib.py disagree on pmpc_scp_cstr: library {lib.pmpc_abi_scp_cstr_size()} bytes, "
                               f"binding {ctypes.sizeof(PmpcScpCstr)}: rebuild the library")
+    if hasattr(lib, "pmpc_scp_loop_device_cstr"):  # (likewise: the keep-out constraint in the library loop)
+        lib.pmpc_keepout_strip_residual_device.argtypes = [vp, sz, ctypes.c_int, sz, sz, sz] + [vp] * 6
+        lib.pmpc_keepout_strip_residual_device.restype = ctypes.c_int
+        lib.pmpc_scp_loop_device_cstr.argtypes = lib.pmpc_scp_loop_device_cost.argtypes + [ctypes.POINTER(PmpcScpCstr), ctypes.POINTER(PmpcScpAug)]
+        lib.pmpc_scp_loop_device_cstr.restype = ctypes.c_int
+        lib.pmpc_scp_loop_follow_ups.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
+        lib.pmpc_scp_loop_follow_ups.restype = None
+        lib.pmpc_abi_scp_aug_size.argtypes = []
+        lib.pmpc_abi_scp_aug_size.restype = sz
+        if lib.pmpc_abi_scp_aug_size() != ctypes.sizeof(PmpcScpAug):
+            raise ImportError(f"{LIB_PATH} and pmpc_amd/_lib.py disagree on pmpc_scp_aug: library {lib.pmpc_abi_scp_aug_size()} bytes, "
+                              f"binding {ctypes.sizeof(PmpcScpAug)}: rebuild the library")
     lib.pmpc_version.argtypes = []
     lib.pmpc_version.restype = ctypes.c_char_p
     # layout check: the library's structs against this binding's mirrors (include/pmpc_abi.h: pmpc_abi_struct_sizes)
@@ -247,6 +266,14 @@ def as_sweep_launches(sweep: str, reset: bool = False):
     out = (ctypes.c_ulonglong * n)()
     lib.pmpc_as_sweep_launches(sw, out, n, int(reset))
     return [int(v) for v in out]
+
+
+def scp_loop_follow_ups(reset: bool = False):
+    """(behind, after): iterations of this process's library SCP loops whose follow-up (residual, next linearisation) was taken as
+    enqueued behind the sub-problem's first batch of rounds / was enqueued after the solve had returned; reset: start counting afresh."""
+    out = (ctypes.c_ulonglong * 2)()
+    load().pmpc_scp_loop_follow_ups(out, int(reset))
+    return int(out[0]), int(out[1])
 
 
 def as_sweep_knobs():

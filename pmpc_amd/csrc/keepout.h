@@ -12,3 +12,8 @@ bool keepout_cstr_valid(const pmpc_scp_cstr *cstr, int xdim);
 void launch_keepout_augment(const pmpc_scp_cstr &cstr, int x, int u, int N, int M, const double *X_prev, const double *f, const double *fx,
                             const double *fu, const double *X_ref, double *f_aug, double *fx_aug, double *fu_aug, double *X_prev_aug,
                             double *X_ref_aug, double *xu_aug, hipStream_t s);
+// the way back: Xo (rows of x) <- the first x entries of every row of X_aug (rows of x + K), and the SCP residual of (Xo, Xp), (Uo, Up) as
+// launch_scp_residual takes it into *out, one launch; zero_out false: the caller vouches that *out is 0
+void launch_keepout_strip_residual(const double *X_aug, double *Xo, const double *Xp, const double *Uo, const double *Up, long long rows, int x,
+                                   int K, int u, double *out, hipStream_t s, bool zero_out = true);
+bool keepout_strip_dims_valid(size_t xdim, int K, size_t udim);  // 1 <= K <= 4, xdim + K <= 16, 1 <= udim <= 16

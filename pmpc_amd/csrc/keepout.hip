@@ -9,6 +9,7 @@
 // pmpc_amd/extra_cstrs.py keepout_augment.
 //
 //   k_keepout_augment   (X_prev, f, fx, fu [, X_ref]) -> (f~, fx~, fu~, X_prev~ [, X_ref~], x_u~[x .. xd))  for M N (particle, stage) units
+//   k_keepout_strip_residual   X~out -> Xo (the first x entries of every row) and the SCP residual of (Xo, Xp), (Uo, Up), below
 //
 // Layout (ABI: blocks column-major, a unit's block of fx is [column][row]):
 //
@@ -122,7 +123,101 @@ __global__ void __launch_bounds__(KO_THREADS) k_keepout_augment(KeepoutArgs a) {
 
 unsigned magic(unsigned d) { return (unsigned)((1ull << 32) / d) + 1u; }
 
+// ---- strip + residual ----------------------------------------------------------------------------------------------------------------
+// The way back from a sub-problem at xd = x + K states: Xo <- the first x entries of every row of X~out, and the SCP residual
+// max(max_rows |Xo - Xp|_2, max_rows |Uo - Up|_2) of the iteration into *out_bits, in ONE pass over X~out (k_scp_residual's result, bit
+// for bit: the same sums in the same order, see row_sq_max).
+//
+// A wave takes floor(64 / d_in) whole rows at a time — d_in <= 16: at least four, 52 to 64 live lanes — so that lane l holds entry
+// l of the wave's range: consecutive lanes load consecutive doubles of X~out (and of U), store nearly consecutive ones of Xo.  (row, entry)
+// of a lane is one multiply-high before the loop; the loop adds a constant to the base.  The row sums go through lane shuffles, LDS
+// holds only the block's 256 maxima.
+struct StripResArgs {
+  const double *X_aug, *Xp, *Uo, *Up;
+  double *Xo;
+  long long rows;
+  int x, xd, u, rpw_x, rpw_u;  // rpw: rows per wave and trip
+  unsigned m_xd, m_u;
+  unsigned long long *out_bits;
+};
+
+// max over the wave's rows of |in[row, :d] - prev[row, :]|^2 (in: rows of d_in >= d doubles; prev, out: rows of d), on the row's first
+// lane.  The sum of a row is residual_block's: four contiguous quarters of q = ceil(d / 4) entries, each an fma chain in entry order from
+// 0, then (a0 + a1) + (a2 + a3) — here every lane of a quarter runs the quarter's chain on values fetched from its lanes.
+template <bool STRIP>
+__device__ __forceinline__ double row_sq_max(const double *in, double *out, const double *prev, long long rows, int d_in, int d, int rpw,
+                                             unsigned m_din, long long gw, long long nw, int lane) {
+  const int row_l = d_in == 1 ? lane : (int)__umulhi((unsigned)lane, m_din), r = lane - row_l * d_in;  // (the constant of d = 1 does not fit 32 bits)
+  const int q = (d + 3) >> 2, head = row_l * d_in;
+  const int sq = (r >= q) + (r >= 2 * q) + (r >= 3 * q);  // the quarter entry r is in
+  const int qs = head + sq * q, qn = min(d, (sq + 1) * q) - sq * q;  // its first lane, its length (<= 0: none, r >= d)
+  double m = 0.0;
+  for (long long g = gw; g * rpw < rows; g += nw) {  // (the trip count is the wave's: the shuffles below are convergent)
+    const long long row = g * rpw + row_l;
+    const bool on = row_l < rpw && row < rows;
+    double t = 0.0;
+    if (on) {
+      const double v = in[row * d_in + r];
+      if (r < d) {
+        if (STRIP) out[row * d + r] = v;
+        t = v - prev[row * d + r];
+      }
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {  // q <= 4 (d <= 16)
+      const double ti = __shfl(t, qs + i, 64);
+      if (i < qn) acc = fma(ti, ti, acc);
+    }
+    double a[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const double ak = __shfl(acc, head + k * q, 64);
+      a[k] = k * q < d ? ak : 0.0;  // (an empty quarter: the lane asked belongs to the auxiliary entries or to the next row)
+    }
+    const double sum = (a[0] + a[1]) + (a[2] + a[3]);
+    if (on && r == 0) m = (sum == sum) ? fmax(m, sum) : INFINITY;  // a NaN trajectory must not look converged
+  }
+  return m;
+}
+
+__global__ void __launch_bounds__(256) k_keepout_strip_residual(StripResArgs a) {
+  __shared__ double sh[256];
+  const int t = threadIdx.x, lane = t & 63;
+  const long long gw = (long long)blockIdx.x * 4 + (t >> 6), nw = (long long)gridDim.x * 4;
+  const double mx = row_sq_max<true>(a.X_aug, a.Xo, a.Xp, a.rows, a.xd, a.x, a.rpw_x, a.m_xd, gw, nw, lane);
+  const double mu = row_sq_max<false>(a.Uo, nullptr, a.Up, a.rows, a.u, a.u, a.rpw_u, a.m_u, gw, nw, lane);
+  sh[t] = sqrt(fmax(mx, mu));
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) sh[t] = fmax(sh[t], sh[t + o]);
+    __syncthreads();
+  }
+  if (t == 0) atomicMax(a.out_bits, (unsigned long long)__double_as_longlong(sh[0]));
+}
+
 }  // namespace
+
+void launch_keepout_strip_residual(const double *X_aug, double *Xo, const double *Xp, const double *Uo, const double *Up, long long rows, int x,
+                                   int K, int u, double *out, hipStream_t s, bool zero_out) {
+  if (rows <= 0) return;
+  if (zero_out) HIP_CHECK(hipMemsetAsync(out, 0, sizeof(double), s));  // (else: the caller vouches that *out is 0)
+  StripResArgs a;
+  a.X_aug = X_aug; a.Xo = Xo; a.Xp = Xp; a.Uo = Uo; a.Up = Up; a.rows = rows; a.x = x; a.xd = x + K; a.u = u;
+  a.rpw_x = 64 / a.xd; a.rpw_u = 64 / u;
+  a.m_xd = magic((unsigned)a.xd); a.m_u = magic((unsigned)u);
+  a.out_bits = (unsigned long long *)out;
+  // one wave per trip of the walk over X~out, four waves a block; capped like the residual kernel's grid (one atomic per block)
+  const long long trips = (rows + a.rpw_x - 1) / a.rpw_x;
+  long long nb = (trips + 3) / 4;
+  const long long cap = rows >= 200000 ? 1024 : 256;
+  if (nb > cap) nb = cap;
+  hipLaunchKernelGGL(k_keepout_strip_residual, dim3((unsigned)nb), dim3(256), 0, s, a);
+}
+
+bool keepout_strip_dims_valid(size_t xdim, int K, size_t udim) {
+  return xdim >= 1 && K >= 1 && K <= KEEPOUT_MAX_K && xdim + (size_t)K <= (size_t)KEEPOUT_MAX_DIM && udim >= 1 && udim <= (size_t)KEEPOUT_MAX_DIM;
+}
 
 bool keepout_cstr_valid(const pmpc_scp_cstr *c, int xdim) {
   if (!c || c->kind != 1 || c->K < 1 || c->K > KEEPOUT_MAX_K || c->pos_dim < 2 || c->pos_dim > 3 || xdim < 1 || xdim + c->K > KEEPOUT_MAX_DIM) return false;
@@ -163,6 +258,21 @@ int pmpc_keepout_augment_device(pmpc_ctx *c, const pmpc_scp_cstr *cstr, size_t x
     ProfScope ps(c, 6);
     launch_keepout_augment(*cstr, (int)xdim, (int)udim, (int)N, (int)M, X_prev, f, fx, fu, X_ref, f_aug, fx_aug, fu_aug, X_prev_aug, X_ref_aug,
                            xu_aug, c->stream);
+    HIP_CHECK(hipGetLastError());
+  } catch (const PmpcHipError &) {
+    return 1;
+  }
+  return 0;
+}
+
+int pmpc_keepout_strip_residual_device(pmpc_ctx *c, size_t xdim, int K, size_t udim, size_t N, size_t M, const double *X_aug, double *X,
+                                       const double *X_prev, const double *U, const double *U_prev, double *out) {
+  if (!c || !keepout_strip_dims_valid(xdim, K, udim) || N == 0 || M == 0 || N > (size_t)0x7fffffff || M > (size_t)0x7fffffff) return 2;
+  if (!X_aug || !X || !X_prev || !U || !U_prev || !out) return 2;
+  try {
+    HIP_CHECK(hipSetDevice(c->device));
+    ProfScope ps(c, 7);
+    launch_keepout_strip_residual(X_aug, X, X_prev, U, U_prev, (long long)M * (long long)N, (int)xdim, K, (int)udim, out, c->stream, true);
     HIP_CHECK(hipGetLastError());
   } catch (const PmpcHipError &) {
     return 1;

@@ -13,6 +13,8 @@
 
 #include "solver_internal.h"
 #include "cost_lin.h"
+#include "keepout.h"
+#include <atomic>
 
 namespace {
 
@@ -787,13 +789,35 @@ int solve_slew_increment_form(pmpc_ctx *c, const pmpc_problem *p, pmpc_info *inf
 // -------------------------------------------------------------------------------------------------
 // SCP loop with the host out of the loop body (built-in dynamics)
 // -------------------------------------------------------------------------------------------------
+static std::atomic<unsigned long long> g_follow_ups[2];  // iterations whose follow-up was taken as enqueued behind the rounds / enqueued after the solve
+void pmpc_scp_loop_follow_ups(unsigned long long *out2, int reset) {
+  for (int k = 0; k < 2; k++) {
+    if (out2) out2[k] = g_follow_ups[k].load();
+    if (reset) g_follow_ups[k].store(0);
+  }
+}
+size_t pmpc_abi_scp_aug_size(void) { return sizeof(pmpc_scp_aug); }
+
 int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmpc_problem *p0, double *f2, double *fx2, double *fu2,
                          int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out) {
-  return pmpc_scp_loop_device_cost(c, model, params, p0, f2, fx2, fu2, steps, first_cold, res, infos, last_in_out, nullptr);
+  return pmpc_scp_loop_device_cstr(c, model, params, p0, f2, fx2, fu2, steps, first_cold, res, infos, last_in_out, nullptr, nullptr, nullptr);
 }
 int pmpc_scp_loop_device_cost(pmpc_ctx *c, int model, const double *params, const pmpc_problem *p0, double *f2, double *fx2, double *fu2,
                               int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out, const pmpc_scp_cost *cost) {
+  return pmpc_scp_loop_device_cstr(c, model, params, p0, f2, fx2, fu2, steps, first_cold, res, infos, last_in_out, cost, nullptr, nullptr);
+}
+// every pointer of the augmented buffers is there
+static bool scp_aug_complete(const pmpc_scp_aug *g) {
+  if (!g || !g->Q || !g->x0 || !g->lx || !g->X_out) return false;
+  for (int k = 0; k < 2; k++)
+    if (!g->f[k] || !g->fx[k] || !g->fu[k] || !g->X_prev[k] || !g->X_ref[k] || !g->xu[k]) return false;
+  return true;
+}
+int pmpc_scp_loop_device_cstr(pmpc_ctx *c, int model, const double *params, const pmpc_problem *p0, double *f2, double *fx2, double *fu2,
+                              int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out, const pmpc_scp_cost *cost,
+                              const pmpc_scp_cstr *cstr, const pmpc_scp_aug *aug) {
   pmpc_problem p = *p0;
+  const int x = (int)p0->xdim, u = (int)p0->udim, N = (int)p0->N, M = (int)p0->M;
   // Built-in cost: the sub-problem of an iteration tracks X_ref - Q^-1 cx(X_prev).  The shifted reference has two sets in the
   // workspace, indexed like F below; shift(set, X) goes behind every linearisation launch, into the set that launch writes.
   const bool with_cost = cost != nullptr && cost->kind != 0;
@@ -801,28 +825,42 @@ int pmpc_scp_loop_device_cost(pmpc_ctx *c, int model, const double *params, cons
   unsigned *cost_bad = nullptr;
   auto shift = [&](int set, const double *X) {  // (inside the linearisation's ProfScope: timed in class 6 with it)
     if (!with_cost) return;
-    launch_obstacle_ref_shift(*cost, (int)p0->xdim, (int)p0->N, (int)p0->M, X, p0->Q, p0->X_ref, Xr[set], cost_bad, c->stream);
+    launch_obstacle_ref_shift(*cost, x, N, M, X, p0->Q, p0->X_ref, Xr[set], cost_bad, c->stream);
   };
   // trajectory buffers A = (X_prev, U_prev), B = (X_out, U_out); linearisation buffers 0 = (f, fx, fu), 1 = (f2, fx2, fu2)
   double *XA = const_cast<double *>(p0->X_prev), *UA = const_cast<double *>(p0->U_prev), *XB = p0->X_out, *UB = p0->U_out;
   double *F[2][3] = {{const_cast<double *>(p0->f), const_cast<double *>(p0->fx), const_cast<double *>(p0->fu)}, {f2, fx2, fu2}};
+  // Built-in constraint (keepout.hip): the sub-problem runs at xd = x + K states on the caller's augmented buffers, of which the
+  // iterate-dependent ones have two sets, indexed like F; augment(set, X) goes behind every linearisation launch and its shift.  The
+  // trajectory pairs stay at x: the sub-problem's states land in aug->X_out and the follow-up strips them into the pair.
+  const bool with_cstr = cstr != nullptr && cstr->kind != 0;
+  const int K = with_cstr ? cstr->K : 0;
+  auto augment = [&](int set, const double *X) {  // (the reference it extends: this iteration's shifted one, else the caller's)
+    if (!with_cstr) return;
+    launch_keepout_augment(*cstr, x, u, N, M, X, F[set][0], F[set][1], F[set][2], with_cost ? Xr[set] : p0->X_ref, aug->f[set], aug->fx[set], aug->fu[set], aug->X_prev[set],
+                           aug->X_ref[set], aug->xu[set], c->stream);
+  };
   const bool soc = p0->soc_u_interior != nullptr || p0->cone_count > 0;
   const bool cone_obj = (p0->flags & PMPC_CONE_OBJECTIVE) != 0;  // the sub-problem is the reference's default path (c_lcone_solve)
   const int jac32 = (p0->flags & PMPC_F32_MATRICES) ? 1 : 0;  // (f / fx / fu scratch sets: fx, fu FLOAT arrays then)
   // Compact Jacobian records (jac_compact.h) instead of the dense fx / fu — a third of the bytes of the one kernel of the step that is
   // bound by its write stream — whenever the coming solve is expected to be a warm attempt of the active-set rounds without a rollout
   // (QpSolve::as_start, use_defect), whose sweeps read the records as they are; a solve that takes another turn expands them first
-  // (QpSolve::densify).  PMPC_LIN_COMPACT=0 switches them off (A/B).
+  // (QpSolve::densify).  PMPC_LIN_COMPACT=0 switches them off (A/B).  Never with a constraint: the augmentation reads dense Jacobians.
   static const bool lin_compact_env = !(getenv("PMPC_LIN_COMPACT") && atoi(getenv("PMPC_LIN_COMPACT")) == 0);
-  const bool compact_ok = lin_compact_env && !cone_obj && !jac32 && !c->multi() && p0->Nc >= 0 && p0->Nc <= 1 &&
-                          jac_compact_dims(model, (int)p0->xdim, (int)p0->udim) && (p0->flags & PMPC_SYMMETRIC_COST) &&
+  const bool compact_ok = lin_compact_env && !with_cstr && !cone_obj && !jac32 && !c->multi() && p0->Nc >= 0 && p0->Nc <= 1 &&
+                          jac_compact_dims(model, x, u) && (p0->flags & PMPC_SYMMETRIC_COST) &&
                           !(p0->flags & (PMPC_HAS_SLEW | PMPC_HAS_SLEW0 | PMPC_FORCE_GENERIC | PMPC_COLD_START)) &&
                           ((p0->flags & PMPC_HAS_UBOUNDS) || soc) && !(p0->barrier_mu > 0.0) && c->opt[OPT_AS_DEFECT] != 0.0 &&
                           c->opt[OPT_AS_WARM] != 0.0 && c->opt[OPT_POLISH_MU] > 0.0;
   bool compact_set[2] = {false, false};  // what the linearisation buffer sets hold
   int done = 0, cur = 0;
-  // (likewise refused: a cost description the kernels cannot run, and a cost next to fp32-stored matrices — the shift reads Q as doubles)
-  if (!model_known(model) || (with_cost && (jac32 || !obstacle_cost_valid(cost, (int)p0->xdim)))) {  // nothing runs (the kernels of some other model would read the caller's arrays with ITS dimensions)
+  // (likewise refused: a cost description the kernels cannot run, and a cost next to fp32-stored matrices — the shift reads Q as doubles;
+  //  a constraint description the kernels cannot run, incomplete augmented buffers, and a constraint next to what rows on the states are
+  //  not solved with: a stage cone, slew penalties, fp32-stored matrices, a sharded context, the squareplus smoothing of the boxes)
+  const bool cstr_refused = with_cstr && (!keepout_cstr_valid(cstr, x) || !keepout_strip_dims_valid(p0->xdim, K, p0->udim) || !scp_aug_complete(aug) || soc ||
+                                          (p0->flags & (PMPC_HAS_SLEW | PMPC_HAS_SLEW0)) || jac32 || c->multi() || p0->smooth_cstr == 1);
+  if (!model_known(model) || (with_cost && (jac32 || !obstacle_cost_valid(cost, x))) || cstr_refused) {  // nothing runs (the kernels of some other model would read the caller's arrays with ITS dimensions)
     if (infos && steps > 0) { memset(&infos[0], 0, sizeof(pmpc_info)); infos[0].status = 2; }
     if (last_in_out) *last_in_out = 0;
     return 0;
@@ -842,10 +880,11 @@ int pmpc_scp_loop_device_cost(pmpc_ctx *c, int model, const double *params, cons
         ProfScope ps(c, 6);
         compact_set[cur] = compact_ok && (done > 0 || !first_cold);
         if (compact_set[cur])
-          launch_linearize_compact(model, (int)p.N, (int)p.M, p.x0, Xp, Up, params, F[cur][0], F[cur][1], nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream);
+          launch_linearize_compact(model, N, M, p0->x0, Xp, Up, params, F[cur][0], F[cur][1], nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream);
         else
-          launch_linearize(model, (int)p.N, (int)p.M, p.x0, Xp, Up, params, F[cur][0], F[cur][1], F[cur][2], c->stream, jac32);
+          launch_linearize(model, N, M, p0->x0, Xp, Up, params, F[cur][0], F[cur][1], F[cur][2], c->stream, jac32);
         shift(cur, Xp);
+        augment(cur, Xp);
       }
       p.f = F[cur][0]; p.fx = F[cur][1]; p.fu = F[cur][2];
       if (with_cost) p.X_ref = Xr[cur];
@@ -855,25 +894,47 @@ int pmpc_scp_loop_device_cost(pmpc_ctx *c, int model, const double *params, cons
       p.flags = p0->flags | PMPC_STATIC_CONS_BOUNDS;
       if (done > 0 || !first_cold) p.flags |= PMPC_PREV_IS_LAST_SOLUTION;
       else p.flags &= ~(unsigned)PMPC_PREV_IS_LAST_SOLUTION;
+      if (with_cstr) {  // the restated problem: rows on the states as upper bounds on the K auxiliary states
+        p.xdim = (size_t)(x + K);
+        p.f = aug->f[cur]; p.fx = aug->fx[cur]; p.fu = aug->fu[cur]; p.X_prev = aug->X_prev[cur];
+        p.X_ref = (with_cost || p0->X_ref) ? aug->X_ref[cur] : nullptr;
+        p.Q = aug->Q; p.x0 = aug->x0; p.lx = aug->lx; p.ux = aug->xu[cur]; p.X_out = aug->X_out;
+        // X_prev~ holds zeros where the last output holds the rows' values: the flag's promise does not hold for the augmented arrays
+        p.flags = (p.flags | PMPC_HAS_XBOUNDS) & ~(unsigned)PMPC_PREV_IS_LAST_SOLUTION;
+      }
       bool res_dirty = false;  // the slot was zeroed with all the others when the loop started; a repeat must zero it again
       auto follow_up = [&, Xp, Up, Xo, Uo](bool with_next_lin) {  // residual of this iteration (+ the next linearisation)
         const bool next = with_next_lin && done + 1 < steps;
+        if (with_cstr) {  // the strip comes first: the residual and the next linearisation read the stripped states
+          {
+            ProfScope ps(c, 7);
+            launch_keepout_strip_residual(aug->X_out, Xo, Xp, Uo, Up, (long long)M * (long long)N, x, K, u, res + done, c->stream, res_dirty);
+            res_dirty = true;
+          }
+          if (next) {
+            ProfScope ps(c, 6);
+            compact_set[cur ^ 1] = false;
+            launch_linearize(model, N, M, p0->x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], c->stream, jac32);
+            shift(cur ^ 1, Xo);
+            augment(cur ^ 1, Xo);
+          }
+          return;
+        }
         if (next && !res_dirty && !c->multi()) {  // both in ONE launch (independent work)
           ProfScope ps(c, 6);
           compact_set[cur ^ 1] = compact_ok;
           if (compact_ok)
-            launch_linearize_compact(model, (int)p.N, (int)p.M, p.x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], Xo, Xp, Uo, Up, (int)p.xdim,
-                                     (int)p.udim, res + done, c->stream);
+            launch_linearize_compact(model, N, M, p0->x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], Xo, Xp, Uo, Up, x, u, res + done, c->stream);
           else
-            launch_linearize_with_residual(model, (int)p.N, (int)p.M, p.x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], Xo, Xp, Uo,
-                                           Up, (int)p.xdim, (int)p.udim, res + done, c->stream, jac32);
+            launch_linearize_with_residual(model, N, M, p0->x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], Xo, Xp, Uo, Up, x, u,
+                                           res + done, c->stream, jac32);
           shift(cur ^ 1, Xo);
           res_dirty = true;
           return;
         }
         {
           ProfScope ps(c, 7);
-          launch_scp_residual(Xo, Xp, Uo, Up, (long long)p.M * (long long)p.N, (int)p.xdim, (int)p.udim, res + done, c->stream, res_dirty);
+          launch_scp_residual(Xo, Xp, Uo, Up, (long long)M * (long long)N, x, u, res + done, c->stream, res_dirty);
           res_dirty = true;
         }
         if (c->multi()) allreduce(c, res + done, 1, ncclFloat64, ncclMax);
@@ -881,9 +942,9 @@ int pmpc_scp_loop_device_cost(pmpc_ctx *c, int model, const double *params, cons
           ProfScope ps(c, 6);
           compact_set[cur ^ 1] = compact_ok;
           if (compact_ok)
-            launch_linearize_compact(model, (int)p.N, (int)p.M, p.x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream);
+            launch_linearize_compact(model, N, M, p0->x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream);
           else
-            launch_linearize(model, (int)p.N, (int)p.M, p.x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], c->stream, jac32);
+            launch_linearize(model, N, M, p0->x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], c->stream, jac32);
           shift(cur ^ 1, Xo);
         }
       };
@@ -895,12 +956,17 @@ int pmpc_scp_loop_device_cost(pmpc_ctx *c, int model, const double *params, cons
       c->post_batch = nullptr;
       c->jac_compact_fx = nullptr;
       if (infos) infos[done] = inf;
-      if (st != 0) break;
+      if (st != 0) {  // (the failed solve left NaN in ITS outputs: with a constraint the states of the pair are not among them)
+        if (with_cstr) launch_fill(Xo, std::numeric_limits<double>::quiet_NaN(), (long long)M * N * x, c->stream);
+        break;
+      }
       if (c->spec_fired && c->spec_ok) {
         lin_ready = true;  // residual and next linearisation are in flight behind the accepted rounds
+        g_follow_ups[0]++;
       } else {
         follow_up(false);  // (a speculative copy, if any, was computed from unfinished outputs: redone; the next linearisation
         lin_ready = false;  //  is enqueued at the top of the next iteration, into the other buffer set)
+        g_follow_ups[1]++;
       }
       cur ^= 1;
     }
@@ -914,9 +980,10 @@ int pmpc_scp_loop_device_cost(pmpc_ctx *c, int model, const double *params, cons
     // undefined); never throws
     try {
       const double nan = std::numeric_limits<double>::quiet_NaN();
-      const long long ex = (long long)p.M * p.N * p.xdim, eu = (long long)p.M * p.N * p.udim;
+      const long long ex = (long long)M * N * x, eu = (long long)M * N * u;
       for (double *b : {XA, XB}) if (b) launch_fill(b, nan, ex, c->stream);
       for (double *b : {UA, UB}) if (b) launch_fill(b, nan, eu, c->stream);
+      if (with_cstr) launch_fill(aug->X_out, nan, (long long)M * N * (x + K), c->stream);
       HIP_WARN(hipStreamSynchronize(c->stream));
     } catch (...) {
     }

@@ -424,7 +424,23 @@ class DeviceSolver:
         self._after(wait_current_stream)
         return out
 
-    def scp_loop(self, model: int, params, steps: int, *, f2, fx2, fu2, first_cold=True, res=None, wait_current_stream=True, cost=None, **kw):
+    def strip_residual(self, X_aug, X, X_prev, U, U_prev, out=None, wait_current_stream=True):
+        """The way back from a sub-problem with K auxiliary states, one launch: `X` (M, N, x) <- `X_aug[..., :x]` (X_aug (M, N, x + K)),
+        and the SCP residual of (X, X_prev), (U, U_prev) as `scp_residual` gives it for the stripped array, a one-element device tensor."""
+        self._need("pmpc_keepout_strip_residual_device")
+        M, N, x = X.shape
+        K = X_aug.shape[-1] - x
+        assert X_aug.shape == (M, N, x + K) and X_prev.shape == X.shape and U.shape == U_prev.shape and U.shape[:2] == (M, N)
+        out = torch.empty((1,), dtype=torch.float64, device=X.device) if out is None else out
+        self._before(wait_current_stream)
+        st = self.lib.pmpc_keepout_strip_residual_device(self.h, x, K, U.shape[-1], N, M, _p(X_aug), _p(X), _p(X_prev), _p(U), _p(U_prev), _p(out))
+        self._after(wait_current_stream)
+        if st != 0:
+            raise RuntimeError(f"pmpc_keepout_strip_residual_device failed ({st}): K outside 1 .. 4, x + K > 16, an empty array, or a HIP error")
+        return out
+
+    def scp_loop(self, model: int, params, steps: int, *, f2, fx2, fu2, first_cold=True, res=None, wait_current_stream=True, cost=None, cstr=None,
+                 aug=None, **kw):
         """`steps` SCP iterations (linearise -> sub-problem -> residual -> swap) for a built-in dynamics model in ONE library
         call: the host is out of the loop body (no Python / ctypes work between iterations, the residual and the next
         linearisation are enqueued behind the sub-problem's rounds before their outcome is read back).  `kw` as for
@@ -433,25 +449,48 @@ class DeviceSolver:
         per-iteration residuals (device tensor), per-iteration info dicts, whether the final iterate is in (X_out, U_out)
         (else in (X_prev, U_prev)), iterations completed.  `cost=dict(kind="obstacles", pos_idx=, centres=, sigma=, w=)`: the built-in
         obstacle cost (`obstacle_cost_grad`) is linearised about every iterate and the sub-problem tracks X_ref - Q^-1 cx (float64 Q
-        with symmetric positive definite blocks; refused with status 2 next to float32 matrices)."""
+        with symmetric positive definite blocks; refused with status 2 next to float32 matrices).
+        `cstr=`: a keep-out constraint, the dict of `prepare_cstr` or its handle, with `aug=pmpc_amd.device_problem.keepout_buffers(problem, K)`
+        (two sets), allocated once by the caller: every iteration's sub-problem runs at x + K states on those buffers (`keepout_augment`'s
+        launch in front of it, `strip_residual`'s behind it); everything this method takes and returns stays at x states.  Refused by
+        the library with status 2: a stage cone, slew penalties, float32 matrices, a sharded context, smooth_cstr="squareplus"."""
         if kw.pop("builtin_cstr", None) is not None:
-            raise ValueError("scp_loop: builtin_cstr is not supported (the library loop has one fixed state dimension, compact Jacobian records and "
-                             "the no-rollout warm start; solve(..., device=..., builtin_cstr=...) carries the constraint)")
+            raise ValueError("scp_loop: builtin_cstr is not supported (the keep-out constraint enters the library loop as cstr=, a dict or the handle "
+                             "of prepare_cstr, with aug=keepout_buffers(...); solve(..., device=..., builtin_cstr=...) carries it in the Python-driven loop)")
         prob, X_out, U_out = self._problem(**kw)
         res = torch.empty((steps,), dtype=torch.float64, device=f2.device) if res is None else res
         infos = (_lib.PmpcInfo * steps)()
         last = ctypes.c_int(0)
+        M, N, x = kw["f"].shape
         if cost is not None:
-            sc, keep = self._scp_cost(cost, kw["f"].shape[1], kw["f"].shape[2], f2.device)
+            sc, keep = self._scp_cost(cost, N, x, f2.device)
+        if cstr is not None:
+            self._need("pmpc_scp_loop_device_cstr")
+            if aug is None:
+                raise ValueError("scp_loop(cstr=...) needs aug=keepout_buffers(problem, K): the augmented buffers, allocated once")
+            own_cstr = not isinstance(cstr, tuple)
+            cs, keep_cstr = self.prepare_cstr(cstr, M, N, x, f2.device)
+            sets = aug["sets"]
+            if aug["K"] != cs.K or len(sets) != 2 or aug["X_out"].shape != (M, N, x + cs.K):
+                raise ValueError(f"scp_loop(cstr=...): aug is not keepout_buffers(problem, K={cs.K}, sets=2) of this problem")
+            two = lambda k: (ctypes.c_void_p * 2)(_p(sets[0][k]), _p(sets[1][k]))
+            ab = _lib.PmpcScpAug(Q=_p(aug["Qa"]), x0=_p(aug["x0"]), lx=_p(aug["lx"]), f=two("f"), fx=two("fx"), fu=two("fu"), X_prev=two("X_prev"),
+                                 X_ref=two("X_ref"), xu=two("xu"), X_out=_p(aug["X_out"]))
         self._before(wait_current_stream)
         jd = kw["fx"].dtype
-        if cost is None:
-            done = self.lib.pmpc_scp_loop_device(self.h, int(model), _p(params), ctypes.byref(prob), _p(f2), _p(fx2, jd), _p(fu2, jd), int(steps),
-                                                 int(bool(first_cold)), _p(res), infos, ctypes.byref(last))
+        head = (self.h, int(model), _p(params), ctypes.byref(prob), _p(f2), _p(fx2, jd), _p(fu2, jd), int(steps), int(bool(first_cold)), _p(res), infos,
+                ctypes.byref(last))
+        if cstr is not None:
+            done = self.lib.pmpc_scp_loop_device_cstr(*head, ctypes.byref(sc) if cost is not None else None, ctypes.byref(cs), ctypes.byref(ab))
+            if cost is not None or own_cstr:
+                self.sync()  # (device arrays that are this call's own: the launches that read them are done before they go)
+            del keep_cstr
+        elif cost is None:
+            done = self.lib.pmpc_scp_loop_device(*head)
         else:
-            done = self.lib.pmpc_scp_loop_device_cost(self.h, int(model), _p(params), ctypes.byref(prob), _p(f2), _p(fx2, jd), _p(fu2, jd), int(steps),
-                                                      int(bool(first_cold)), _p(res), infos, ctypes.byref(last), ctypes.byref(sc))
+            done = self.lib.pmpc_scp_loop_device_cost(*head, ctypes.byref(sc))
             self.sync()  # (the cost's device arrays are this call's own: the launches that read them are done before they go)
+        if cost is not None:
             del keep
         self._after(wait_current_stream)
         if cost is not None:

@@ -3,7 +3,8 @@
 `build_problem` is what `solve(..., device=...)` (pmpc_amd/scp_device.py) and `MPCController` (pmpc_amd/mpc.py) share: argument
 conversion, the ABI transposes, the reading of `solver_settings`, slew tensors, the `extra_cstrs` -> stage-cone parse.  It is plain
 tensor work: no `DeviceSolver`, no library call, no stream — with `device="cpu"` it builds the same object out of CPU tensors.
-`keepout_static` is the part of the keep-out augmentation (pmpc_amd.extra_cstrs.keepout_augment) that does not change with the iterate.
+`keepout_static` is the part of the keep-out augmentation (pmpc_amd.extra_cstrs.keepout_augment) that does not change with the iterate;
+`keepout_buffers` adds the arrays that do, once (the Python-driven loop) or twice (the library loop, `DeviceSolver.scp_loop(cstr=, aug=)`).
 """
 from __future__ import annotations
 
@@ -141,3 +142,17 @@ def keepout_static(p: DeviceProblem, K: int) -> Dict[str, torch.Tensor]:
     x0 = mk(M, xd, fill=0.0)
     x0[:, :xdim] = p.x0
     return dict(Qa=Qa, x0=x0, lx=lx, xu=xu)
+
+
+def keepout_buffers(p: DeviceProblem, K: int, sets: int = 2) -> Dict[str, Any]:
+    """Every array of the problem at xd = xdim + K states, allocated once: `keepout_static`'s `Qa`, `x0`, `lx`; `sets`: that many
+    dicts of the iterate-dependent arrays `f`, `fx`, `fu`, `X_prev`, `X_ref` (uninitialised: the augmentation kernel writes them) and
+    `xu` (each set a copy of its own of the static upper bounds: the kernel writes the K auxiliary entries of every row); `X_out`
+    (M, N, xd), the sub-problem's output.  The library loop takes two sets (include/pmpc_abi.h pmpc_scp_aug): the augmentation it
+    enqueues behind a sub-problem's rounds must not touch what a continued solve still reads."""
+    M, N, u, xd = p.M, p.N, p.udim, p.xdim + K
+    static = keepout_static(p, K)
+    mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=p.Qa.device)
+    one = lambda k: dict(f=mk(M, N, xd), fx=mk(M, N, xd, xd), fu=mk(M, N, u, xd), X_prev=mk(M, N, xd), X_ref=mk(M, N, xd),
+                         xu=static["xu"] if k == 0 else static["xu"].clone())
+    return dict(Qa=static["Qa"], x0=static["x0"], lx=static["lx"], sets=[one(k) for k in range(int(sets))], X_out=mk(M, N, xd), K=int(K))

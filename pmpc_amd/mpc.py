@@ -13,6 +13,12 @@ Every step's first SCP iteration runs with `first_cold=True`: after a shift the 
 no-rollout warm start and the compact Jacobian records begin at the second iteration of each step.  (Shifting the solver's active-set
 memory along with the plan is not done.)
 
+`keepout=dict(pos_idx=, centres=, radius=)` is the hard keep-out constraint of `solve(..., device=..., builtin_cstr=...)` (1 to 4 balls in the
+position sub-space `pos_idx`; centres `(K, pos_dim)`, `(N, K, pos_dim)` per stage or `(M, N, K, pos_dim)` per particle and stage) carried
+through the library loop: every sub-problem runs at `xdim + K` states on augmented buffers the constructor allocates once, the plan
+stays at `xdim`.  `set_keepout` writes new centres / radii into the resident arrays.  Refused next to it, before a device is touched: a
+stage cone (`soc=` / `extra_cstrs`), slew penalties, a sharded context, `xdim + K > 16`.
+
 Refused with a ValueError (the library loop has no place for them): a Python `f_fx_fu_fn` / `lin_cost_fn` / `cost_fn`, `extra_cstrs_fns`,
 filters, `solver_state`, a sharded context, and `solver_settings` keys other than `solver`, `Nc`, `smooth_alpha`, `slew_reg`,
 `extra_cstrs`, `soc_u_interior`.  `soc=` / `solver_settings["extra_cstrs"]` (one stage-wise second-order cone) are taken as in
@@ -27,7 +33,7 @@ import numpy as np
 import torch
 
 from .device import DeviceSolver
-from .device_problem import build_problem
+from .device_problem import build_problem, keepout_buffers
 from .dynamics import model_id
 
 _SETTINGS = ("solver", "Nc", "smooth_alpha", "slew_reg", "extra_cstrs", "soc_u_interior")
@@ -37,16 +43,20 @@ class MPCController:
     def __init__(self, builtin_model=None, params=None, Q=None, R=None, X_ref=None, U_ref=None, u_l=None, u_u=None, x_l=None, x_u=None,
                  reg_x: float = 1e0, reg_u: float = 1e-2, solver_settings: Optional[Dict[str, Any]] = None, builtin_cost: Optional[Dict[str, Any]] = None,
                  slew_rate: Optional[float] = None, u0_slew=None, soc: Optional[Dict[str, Any]] = None, device="cuda",
-                 solver: Optional[DeviceSolver] = None, **unsupported):
+                 solver: Optional[DeviceSolver] = None, keepout: Optional[Dict[str, Any]] = None, **unsupported):
         if builtin_model is None:
             raise ValueError("MPCController needs builtin_model=: a Python f_fx_fu_fn cannot enter the library's SCP loop")
         if unsupported.get("builtin_cstr") is not None:
-            raise ValueError("MPCController: builtin_cstr is not supported (the library's SCP loop has one fixed state dimension; "
-                             "pmpc_amd.solve(..., device=..., builtin_cstr=...) carries the keep-out constraint)")
+            raise ValueError("MPCController: builtin_cstr is not supported (the controller takes the keep-out constraint as "
+                             "keepout=dict(pos_idx=, centres=, radius=); pmpc_amd.solve(..., device=..., builtin_cstr=...) carries it in one solve)")
         bad = [k for k, v in unsupported.items() if v is not None and v != ""]
         if bad:
             raise ValueError(f"MPCController does not support {sorted(bad)}; the host loop pmpc_amd.solve(...) has the host-only features")
         settings = dict(solver_settings or {})
+        if keepout is not None:  # what the constraint is refused with, for scp_device.py's reasons: before any device is touched
+            from .scp_device import _refuse_with_cstr
+
+            _refuse_with_cstr(settings, soc, slew_rate, u0_slew, solver)
         bad = [k for k in settings if k not in _SETTINGS]
         if bad:
             raise ValueError(f"MPCController: solver_settings {sorted(bad)} are not taken by the library's SCP loop (taken: {_SETTINGS})")
@@ -57,6 +67,14 @@ class MPCController:
         self.device = dev
         if np.ndim(Q) != 4 or np.ndim(R) != 4:
             raise ValueError("MPCController: Q (M, N, x, x) and R (M, N, u, u)")
+        if keepout is not None:  # a description the kernels cannot run: likewise before any device is touched
+            from .extra_cstrs import _keepout_arrays
+
+            keepout = dict(keepout, kind=keepout.get("kind", "keepout"))
+            host = {k: v.cpu().numpy() if torch.is_tensor(v) else v for k, v in keepout.items()}
+            _, _, rad = _keepout_arrays(host, np.shape(Q)[0], np.shape(Q)[1], np.shape(Q)[-1])
+            if np.shape(Q)[-1] + len(rad) > 16:
+                raise ValueError(f"keep-out constraint: {np.shape(Q)[-1]} states + {len(rad)} auxiliary states exceed the solver's 16")
         if solver is None:
             from .scp_device import _solver_for
 
@@ -86,6 +104,13 @@ class MPCController:
         self._res = mk(64)
         self._cost = s.prepare_cost(builtin_cost, N, x, dev) if builtin_cost is not None else None
         self._kw = dict(p.solve_kw(), x0=self._x0, X_ref=self.X_ref, U_ref=self.U_ref, **soc_kw)
+        # the keep-out constraint: the descriptor with its device arrays (`set_keepout` writes them in place) and the augmented buffers
+        # of the library loop, both made once; x0~ = [x0 | 0] is refreshed from x0 every step
+        self._cstr = self._aug = None
+        if keepout is not None:
+            self._cstr = s.prepare_cstr(keepout, M, N, x, dev)
+            p.x0 = self._x0
+            self._aug = keepout_buffers(p, self._cstr[0].K, sets=2)
         torch.cuda.current_stream(dev).synchronize()  # (the uploads above ran on the caller's stream; the kernels read them on the solver's)
         self.reset()
 
@@ -130,6 +155,25 @@ class MPCController:
                 self._load(self.U_ref, U_ref)
         s._after()
 
+    def set_keepout(self, centres=None, radius=None):
+        """New centres and / or radii of the keep-out balls, copied into the resident arrays on the solver's stream (None: unchanged).
+        Shapes as at construction: a controller built with static centres (K, pos_dim) keeps static ones.  Per-stage or per-particle
+        centres are NOT moved along with the plan by `step`'s shift: stage j of the array is stage j of the next plan as it is, so a
+        caller with moving obstacles sets them before every step."""
+        if self._cstr is None:
+            raise ValueError("MPCController.set_keepout: the controller was built without keepout=")
+        cen, rad = self._cstr[1]
+        if radius is not None and not bool((torch.as_tensor(radius) > 0).all()):
+            raise ValueError("keep-out constraint: every radius must be positive")
+        s = self.solver
+        s._before()
+        with torch.cuda.stream(s.stream):
+            if centres is not None:
+                self._load(cen, centres)
+            if radius is not None:
+                self._load(rad, radius)
+        s._after()
+
     # ---- one MPC step ----------------------------------------------------------------------------------------
     def step(self, x0, iterations: int = 3, shift: int = 1, U_tail=None, return_torch: bool = False):
         """x0 (x,) or (M, x), numpy or GPU tensor -> (u0, info): u0 = U[:, 0, :] of the new plan, a copy (M, u) (numpy unless
@@ -146,6 +190,8 @@ class MPCController:
         with torch.cuda.stream(s.stream):
             x0 = torch.as_tensor(np.asarray(x0) if not torch.is_tensor(x0) else x0, dtype=torch.float64)
             self._x0.copy_(x0.to(self.device).reshape(-1, self.xdim).expand(self.M, self.xdim))
+            if self._aug is not None:
+                self._aug["x0"][:, :self.xdim].copy_(self._x0)
             if U_tail is not None:
                 U_tail = torch.as_tensor(np.asarray(U_tail) if not torch.is_tensor(U_tail) else U_tail, dtype=torch.float64).to(self.device).contiguous()
         if self._fresh:
@@ -163,7 +209,7 @@ class MPCController:
         f, fx, fu, f2, fx2, fu2 = self._lin
         res, infos, last_in_out, done = s.scp_loop(self.model, self.params, iterations, f=f, fx=fx, fu=fu, f2=f2, fx2=fx2, fu2=fu2, X_prev=Xa, U_prev=Ua,
                                                    X_out=Xb, U_out=Ub, first_cold=True, res=self._res[:iterations], cost=self._cost,
-                                                   wait_current_stream=False, **slew0, **self._kw)
+                                                   cstr=self._cstr, aug=self._aug, wait_current_stream=False, **slew0, **self._kw)
         if last_in_out:
             self._cur ^= 1
         ok = done == iterations

@@ -41,7 +41,7 @@ from typing import Any, Callable, Dict, Optional
 import torch
 
 from .device import DeviceSolver
-from .device_problem import build_problem, keepout_static
+from .device_problem import build_problem, keepout_buffers
 from .utils import TablePrinter
 
 _solvers: Dict[int, DeviceSolver] = {}
@@ -112,11 +112,8 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
     if builtin_cstr is not None:
         _refuse_with_cstr(solver=s)
         cstr_handle = s.prepare_cstr(builtin_cstr, M, N, xdim, dev)
-        xd = xdim + cstr_handle[0].K
-        static = keepout_static(p, cstr_handle[0].K)
-        mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
-        aug = dict(f=mk(M, N, xd), fx=mk(M, N, xd, xd), fu=mk(M, N, udim, xd), X_prev=mk(M, N, xd), X_ref=mk(M, N, xd), xu=static["xu"])
-        Xs_aug = mk(M, N, xd)
+        static = keepout_buffers(p, cstr_handle[0].K, sets=1)  # (one set: nothing of the next iteration is enqueued behind this loop's solves)
+        aug, Xs_aug = static["sets"][0], static["X_out"]
     it, max_res = 0, math.inf
     s.stream.wait_stream(torch.cuda.current_stream(dev))  # the set-up above ran on the caller's stream
     while it < max_it:

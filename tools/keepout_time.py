@@ -1,12 +1,13 @@
 #!/usr/bin/env python
 """What the keep-out constraint costs: one launch of `k_keepout_augment` next to one linearisation launch at the same shape, against the
-time its bytes alone would take at a given streaming rate, and the per-iteration time of `pmpc_amd.solve(..., device="cuda")` with and
-without `builtin_cstr`.  Not a benchmark of the solver (bench.py is); the numbers of CHANGELOG.md's keep-out entry come from here.
+time its bytes alone would take at a given streaming rate, one launch of the strip-and-residual kernel next to the plain residual
+launch, and the per-iteration time of `pmpc_amd.solve(..., device="cuda")` with and without `builtin_cstr` and of the library loop
+(`DeviceSolver.scp_loop(cstr=, aug=)`, buffers allocated once as `MPCController` does) with the constraint.  Not a benchmark of the solver (bench.py is); the numbers of CHANGELOG.md's keep-out entry come from here.
 
     python tools/keepout_time.py --model quadrotor --M 4096 --N 50 --K 2
 
 Kernel times: HIP events on the solver's stream around single launches, both kernels warmed first and alternating in one loop.
-Iteration times: host clock around `solve` calls of --iterations iterations (res_tol = 0; each ends with a device->host read), the two
+Iteration times: host clock around calls of --iterations iterations (res_tol = 0; each ends with a device->host read), the
 versions alternating.  Prints one JSON line."""
 import argparse
 import ctypes
@@ -49,6 +50,9 @@ def kernel_times(solver, mid, d, cstr, reps=30):
             "keepout_augment": lambda: solver.lib.pmpc_keepout_augment_device(
                 solver.h, ctypes.byref(handle[0]), x, U.shape[-1], N, M,
                 *[ctypes.c_void_p(t.data_ptr()) for t in (X, f, fx, fu, d["X_ref"], out["f"], out["fx"], out["fu"], out["X_prev"], out["X_ref"], out["xu"])])}
+    Xs, Us, res = torch.empty_like(X), U + 0.5, torch.empty((1,), dtype=torch.float64, device=X.device)
+    jobs["scp_residual"] = lambda: solver.scp_residual(Xs, X, Us, U, out=res, wait_current_stream=False)
+    jobs["strip_residual"] = lambda: solver.strip_residual(out["X_prev"], Xs, X, Us, U, out=res, wait_current_stream=False)
     times = {k: [] for k in jobs}
     with torch.cuda.stream(solver.stream):
         for rep in range(reps + 5):
@@ -61,6 +65,38 @@ def kernel_times(solver, mid, d, cstr, reps=30):
                 if rep >= 5:  # (the first five rounds warm both kernels)
                     times[k].append(1e3 * e0.elapsed_time(e1))
     return {k: _stats(v) for k, v in times.items()}
+
+
+def library_leg(prob, model, cstr, iterations):
+    """A callable that runs `iterations` iterations of the library loop with the constraint from the problem's start iterate and returns
+    (X (M, N, x) numpy or None, infos): every buffer allocated here, once; a call copies the start iterate in and reads the residuals back."""
+    import torch
+
+    from pmpc_amd.device import DeviceSolver
+    from pmpc_amd.device_problem import build_problem, keepout_buffers
+
+    s = DeviceSolver(0)
+    p = build_problem(prob["Q"], prob["R"], prob["x0"], prob["X_ref"], prob["U_ref"], prob["X_prev"], prob["U_prev"], None, None, prob["u_l"], prob["u_u"],
+                      prob["reg_x"], prob["reg_u"], None, None, dict(solver="osqp", Nc=1), None, model, prob["params"], "cuda")
+    M, N, x, u = p.M, p.N, p.xdim, p.udim
+    mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device="cuda")
+    handle = s.prepare_cstr(cstr, M, N, x)
+    aug = keepout_buffers(p, handle[0].K)
+    lin = dict(f=mk(M, N, x), fx=mk(M, N, x, x), fu=mk(M, N, u, x), f2=mk(M, N, x), fx2=mk(M, N, x, x), fu2=mk(M, N, u, x))
+    Xa, Ua, Xb, Ub, res = mk(M, N, x), mk(M, N, u), mk(M, N, x), mk(M, N, u), mk(iterations)
+    torch.cuda.synchronize()
+
+    def run():
+        Xa.copy_(p.X_prev)
+        Ua.copy_(p.U_prev)
+        _, infos, last, done = s.scp_loop(p.model, p.params, iterations, X_prev=Xa, U_prev=Ua, X_out=Xb, U_out=Ub, X_ref=p.X_ref, U_ref=p.U_ref, first_cold=True,
+                                          res=res, cstr=handle, aug=aug, **lin, **p.solve_kw())
+        r = res.cpu()  # (the device->host read that ends the call, as solve's `hist` row does)
+        if done != iterations or not bool(torch.isfinite(r).all()):
+            return None, infos
+        return (Xb if last else Xa).cpu().numpy(), infos
+
+    return run
 
 
 def main():
@@ -99,11 +135,25 @@ def main():
     if not args.no_solve:
         common = dict(X_ref=prob["X_ref"], U_ref=prob["U_ref"], X_prev=prob["X_prev"], U_prev=prob["U_prev"], u_l=prob["u_l"], u_u=prob["u_u"], reg_x=prob["reg_x"],
                       reg_u=prob["reg_u"], solver_settings=dict(solver="osqp", Nc=1), max_it=args.iterations, res_tol=0.0, verbose=False)
-        versions = {"without": {}, "with": dict(builtin_cstr=cstr)}
+        versions = {"without": {}, "with": dict(builtin_cstr=cstr), "library": None}
+        lib_run = library_leg(prob, args.model, cstr, args.iterations)
         t = {k: [] for k in versions}
         info = {}
         for rep in range(args.solves + 2):
             for k, extra in versions.items():
+                if k == "library":
+                    t0 = time.perf_counter()
+                    Xl, infos = lib_run()
+                    t1 = time.perf_counter()
+                    if Xl is None:
+                        info[k] = dict(failed=True)
+                        continue
+                    if rep >= 2:
+                        t[k].append(1e3 * (t1 - t0) / args.iterations)
+                    c, r = cstr["centres"], cstr["radius"]
+                    info[k] = dict(fast_path=[int(i["fast_path"]) for i in infos], active_set_rounds=[int(i["active_set_rounds"]) for i in infos],
+                                   ipm_iters=[int(i["ipm_iters"]) for i in infos], clearance=float((np.linalg.norm(Xl[:, :, None, :pos_dim] - c, axis=-1) - r).min()))
+                    continue
                 t0 = time.perf_counter()
                 X, U, data = pmpc_amd.solve(None, prob["Q"], prob["R"], prob["x0"], device="cuda", builtin_model=args.model, params=prob["params"], **extra, **common)
                 t1 = time.perf_counter()
@@ -118,8 +168,10 @@ def main():
                     c, r = cstr["centres"], cstr["radius"]
                     info[k]["clearance"] = float((np.linalg.norm(X[:, 1:, None, :pos_dim] - c, axis=-1) - r).min())
         result["iteration_ms"] = {k: _stats(v) for k, v in t.items() if v}
-        if len(result["iteration_ms"]) == 2:
+        if "with" in result["iteration_ms"] and "without" in result["iteration_ms"]:
             result["slowdown"] = result["iteration_ms"]["with"]["median"] / result["iteration_ms"]["without"]["median"]
+        if "with" in result["iteration_ms"] and "library" in result["iteration_ms"]:
+            result["library_over_python_driven"] = result["iteration_ms"]["library"]["median"] / result["iteration_ms"]["with"]["median"]
         result["solver_info"] = info
     print(json.dumps(result))
 

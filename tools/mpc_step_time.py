@@ -4,6 +4,7 @@ shifted on the host, and the launch times of the rollout / plan-shift kernels ne
 solver (bench.py is); the numbers of CHANGELOG.md's MPCController entry come from here.
 
     python tools/mpc_step_time.py --model quadrotor --M 4096 --N 50 --steps 50 --iterations 3
+    python tools/mpc_step_time.py --model bicycle --keepout 2        # both versions with a keep-out constraint of 2 balls per particle
 
 Kernel times: HIP events on the solver's stream around single launches, all shapes warmed first, the kernels alternating in one loop.
 Step times: host clock around calls that end with a device->host read (both are synchronous), the two versions alternating step by step
@@ -56,6 +57,8 @@ def main():
     ap.add_argument("--steps", type=int, default=50, help="timed MPC steps per version (after --warmup)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iterations", type=int, default=3)
+    ap.add_argument("--keepout", type=int, default=0, metavar="K", help="K balls per particle beside the start plan (tools/keepout_time.py make_cstr): "
+                    "MPCController(keepout=...) against solve(builtin_cstr=...)")
     ap.add_argument("--no-solve", action="store_true", help="leave the pmpc_amd.solve version out (kernel times and the controller only)")
     args = ap.parse_args()
 
@@ -72,27 +75,43 @@ def main():
 
     common = dict(X_ref=prob["X_ref"], U_ref=prob["U_ref"], u_l=prob["u_l"], u_u=prob["u_u"], reg_x=prob["reg_x"], reg_u=prob["reg_u"],
                   solver_settings=dict(solver="osqp", Nc=1))
-    ctl = pmpc_amd.MPCController(builtin_model=args.model, params=prob["params"], Q=prob["Q"], R=prob["R"], solver=solver, **common)
+    ctl_kw, solve_kw = {}, {}
+    if args.keepout:
+        from keepout_time import make_cstr  # (tools/ is the script's directory)
+
+        cstr = make_cstr(prob, args.keepout, 3 if args.model == "quadrotor" else 2)
+        ctl_kw, solve_kw = dict(keepout={k: cstr[k] for k in ("pos_idx", "centres", "radius")}), dict(builtin_cstr=cstr)
+        result["keepout"] = args.keepout
+    ctl = pmpc_amd.MPCController(builtin_model=args.model, params=prob["params"], Q=prob["Q"], R=prob["R"], solver=solver, **ctl_kw, **common)
     ctl.reset(X_prev=prob["X_prev"], U_prev=prob["U_prev"])
     Xs, Us = prob["X_prev"], prob["U_prev"]  # the solve version's warm start
     rng = np.random.default_rng(0)
     x0 = prob["x0"][0]
     t_ctl, t_solve, first, later = [], [], [], []
+    fresh, restarts = True, 0  # (fresh: the solve version has no plan to shift)
     for k in range(args.warmup + args.steps):
         t0 = time.perf_counter()
         u0, info = ctl.step(x0, iterations=args.iterations)
         t1 = time.perf_counter()
-        if u0 is None:
-            raise SystemExit(f"MPCController.step failed in step {k}: {info}")
-        if not args.no_solve:
+        X = 0
+        if u0 is not None and not args.no_solve:
             t2 = time.perf_counter()
-            if k > 0:
+            if not fresh:
                 Xs, Us, _ = dyn.shift_plan(mid, Xs, Us, prob["params"], s=1)
             X, U, data = pmpc_amd.solve(None, prob["Q"], prob["R"], np.tile(x0, (args.M, 1)), device="cuda", builtin_model=args.model, params=prob["params"],
-                                        X_prev=Xs, U_prev=Us, max_it=args.iterations, res_tol=0.0, verbose=False, **common)  # (on the package's own context)
+                                        X_prev=Xs, U_prev=Us, max_it=args.iterations, res_tol=0.0, verbose=False, **solve_kw, **common)  # (on the package's own context)
             t3 = time.perf_counter()
-            if X is None:
-                raise SystemExit(f"pmpc_amd.solve failed in step {k}")
+        if u0 is None or X is None:
+            # a hard constraint can leave a shifted plan no feasible step (the particles share particle 0's measured state, not their
+            # balls): the episode starts over from the problem's start plan, the failed step is not timed
+            if not args.keepout or fresh:
+                raise SystemExit(f"step {k} failed: {info}")
+            restarts += 1
+            ctl.reset(X_prev=prob["X_prev"], U_prev=prob["U_prev"])
+            Xs, Us, x0, fresh = prob["X_prev"], prob["U_prev"], prob["x0"][0], True
+            continue
+        fresh = False
+        if not args.no_solve:
             Xs, Us = X[:, 1:], U
         if k >= args.warmup:
             t_ctl.append(1e3 * (t1 - t0))
@@ -100,7 +119,10 @@ def main():
                 t_solve.append(1e3 * (t3 - t2))
             first.append((info["infos"][0]["active_set_rounds"], info["infos"][0]["ipm_iters"]))
             later += [(i["active_set_rounds"], i["ipm_iters"]) for i in info["infos"][1:]]
-        x0 = F(x0, u0[0], prob["params"][0])[0] + 0.01 * rng.standard_normal(x0.shape)
+        # (with a keep-out constraint the plant is the model: a disturbed state can sit where the linearised rows leave no feasible first stage)
+        x0 = F(x0, u0[0], prob["params"][0])[0] + (0.0 if args.keepout else 0.01) * rng.standard_normal(x0.shape)
+    if args.keepout:
+        result["episode_restarts"] = restarts
     result["controller_step_ms"] = _stats(t_ctl)
     if t_solve:
         result["solve_step_ms"] = _stats(t_solve)
