@@ -303,6 +303,37 @@ int pmpc_rollout_device(pmpc_ctx *ctx, int model, size_t N, size_t M, const doub
 int pmpc_shift_plan_device(pmpc_ctx *ctx, int model, size_t N, size_t M, size_t s, const double *X, const double *U,
                            const double *params, const double *U_tail, double *X_new, double *U_new, double *um1_new);
 
+/* The control-box statuses of a plan moved s stages on together with its controls, 1 <= s < N, into the boxes of the stages they
+ * arrive at (the boxes do not move with the horizon) — never in place.  act (M, N, udim) ints: 0 free, 1 on the lower, 2 on the upper
+ * bound; U, lo, hi (M, N, udim) (lo / hi NULL: no bound on that side); Nc: consensus stages (< 0 or > N: N).  Entry (i, j, r):
+ *   source  z = U[i, j + s, r], a = act[i, j + s, r]                                     for j < N - s
+ *           z = U_tail[i, j - (N - s), r], a = 0  (U_tail (M, s, udim); NULL: stage N - 1 of U and act, hold)  for j >= N - s
+ *           on a consensus stage j < Nc: particle 0's source, and l = lo[0, j, r], h = hi[0, j, r]; else l = lo[i, j, r], h = hi[i, j, r]
+ *   l > h or z NaN:  U_new = z, act_new = 0   (the solve's own check refuses such a problem)
+ *   else  zc = z < l ? l : (z > h ? h : z);  act_new = 1 if zc == l and (a == 1 or z < l), else 2 if zc == h and (a == 2 or z > h), else 0;
+ *         U_new = zc
+ * (U_new, act_new) is then a start the no-rollout warm start of the active-set rounds accepts: every held control exactly on its
+ * bound, every free one inside its box, the consensus stages uniform over the particles.  pmpc_amd.dynamics.shift_active_set is the
+ * specification.  One launch, asynchronous on pmpc_stream().  Returns 0; 2 and launches nothing for N == 0, M == 0, udim == 0, s
+ * outside 1 .. N - 1, U_new == U, act_new == act or a null pointer among U, act, U_new, act_new; 1 on a HIP error. */
+int pmpc_shift_active_set_device(pmpc_ctx *ctx, size_t N, size_t M, size_t udim, long long Nc, size_t s, const double *U,
+                                 const double *U_tail, const int *act, const double *lo, const double *hi, double *U_new, int *act_new);
+
+/* The same launch applied to the set the context's last accepted solve stored: its statuses are moved into a second buffer of the
+ * workspace and the two are swapped; U is the plan BEFORE the shift (the source pair of pmpc_shift_plan_device), U_new the shifted
+ * plan's controls (written behind that launch on the same stream), lo / hi the lu / uu of the problem.  The next
+ * pmpc_scp_loop_device of this shape may then run with first_cold = 0: its first solve takes the warm path of every later one.
+ * *shifted = 1 if a set of M N udim statuses was stored; else *shifted = 0, nothing is launched and U_new is untouched (no accepted
+ * active-set solve since the context was made or since a solve that ended otherwise; a sharded context).  The stored solution, the
+ * predicted round count and every other warm-start memory stay as they are: stage-cone, state-row and epigraph multipliers are NOT
+ * moved — a caller with those keeps first_cold = 1.  Returns as above (2 also for shifted == NULL). */
+int pmpc_warm_shift_device(pmpc_ctx *ctx, size_t N, size_t M, size_t udim, long long Nc, size_t s, const double *U, const double *U_tail,
+                           const double *lo, const double *hi, double *U_new, int *shifted);
+
+/* Copy of the stored statuses into act_out (n ints, device), for tests; asynchronous on pmpc_stream().  Returns 2 if nothing is stored
+ * or the stored set does not hold n statuses. */
+int pmpc_warm_set_read_device(pmpc_ctx *ctx, int *act_out, size_t n);
+
 /* Compact Jacobian records of a built-in model — what pmpc_scp_loop_device writes into its fx scratch arrays instead of the dense
  * stacks when the coming solve is a warm attempt of the active-set rounds (PMPC_LIN_COMPACT=0 switches that off).  For tests and
  * tools: the linearisation into jc (pmpc_jac_compact_doubles(model, N, M) doubles; f dense), the expansion of jc into the dense

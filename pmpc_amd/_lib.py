@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "pmpc_rollout_device", "pmpc_shift_plan_device",
     "pmpc_keepout_augment_device", "pmpc_abi_scp_cstr_size",
     "pmpc_keepout_strip_residual_device", "pmpc_scp_loop_device_cstr", "pmpc_abi_scp_aug_size", "pmpc_scp_loop_follow_ups",
+    "pmpc_shift_active_set_device", "pmpc_warm_shift_device", "pmpc_warm_set_read_device",
 ]
 
 
@@ -202,6 +203,13 @@ def load():
         if lib.pmpc_abi_scp_aug_size() != ctypes.sizeof(PmpcScpAug):
             raise ImportError(f"{LIB_PATH} and pmpc_amd/_lib.py disagree on pmpc_scp_aug: library {lib.pmpc_abi_scp_aug_size()} bytes, "
                               f"binding {ctypes.sizeof(PmpcScpAug)}: rebuild the library")
+    if hasattr(lib, "pmpc_warm_shift_device"):  # (likewise: the active set moved along with the plan)
+        lib.pmpc_shift_active_set_device.argtypes = [vp, sz, sz, sz, ll, sz] + [vp] * 7
+        lib.pmpc_shift_active_set_device.restype = ctypes.c_int
+        lib.pmpc_warm_shift_device.argtypes = [vp, sz, sz, sz, ll, sz] + [vp] * 5 + [ctypes.POINTER(ctypes.c_int)]
+        lib.pmpc_warm_shift_device.restype = ctypes.c_int
+        lib.pmpc_warm_set_read_device.argtypes = [vp, vp, sz]
+        lib.pmpc_warm_set_read_device.restype = ctypes.c_int
     lib.pmpc_version.argtypes = []
     lib.pmpc_version.restype = ctypes.c_char_p
     # layout check: the library's structs against this binding's mirrors (include/pmpc_abi.h: pmpc_abi_struct_sizes)

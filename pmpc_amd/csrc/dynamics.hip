@@ -430,6 +430,44 @@ __global__ void __launch_bounds__(ROLL_LANES) k_shift_plan(int N, int M, int s, 
   }
 }
 
+// The control-box statuses of a plan moved s stages on together with its controls (pmpc_amd.dynamics.shift_active_set is the
+// specification): entry (i, j, r) takes control and status of stage j + s (tail j >= N - s: U_tail with status 0; null: stage N - 1,
+// hold), on a consensus stage j < Nc from particle 0 and into particle 0's box; the control is clamped into the box of stage j, the
+// status kept where the control is still on that bound, set where the clamp moved it, 0 otherwise.  (Un, actn) is then a base point
+// the first round of the no-rollout warm start accepts (kernels_as.hip, k_fwd_as<DEFECT>).  One thread per entry, consecutive lanes
+// consecutive entries; strictly out of place: every input is read-only, so particle 0's source is never one this launch writes.
+__global__ void __launch_bounds__(256) k_shift_active_set(int N, int UD, int Nc, int s, long long n, const double *U, const double *U_tail, const int *act,
+                                                          const double *lo, const double *hi, double *Un, int *actn) {
+  const int keep = N - s, row = N * UD;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += stride) {
+    const long long i = e / row;
+    const int q = (int)(e - i * row), j = q / UD, r = q - j * UD;
+    const long long is = j < Nc ? 0 : i;  // the particle whose source and box the entry takes
+    double z;
+    int a;
+    if (j >= keep && U_tail) {
+      z = U_tail[(is * s + (j - keep)) * UD + r];
+      a = 0;
+    } else {
+      const long long src = (is * N + (j < keep ? j + s : N - 1)) * UD + r;
+      z = U[src];
+      a = act[src];
+    }
+    const long long b = (is * N + j) * UD + r;
+    const double l = lo ? lo[b] : -INFINITY, h = hi ? hi[b] : INFINITY;
+    double zc = z;
+    int an = 0;
+    if (!(l > h) && !(z != z)) {  // (an empty box or a NaN passes through: the solve's own check refuses it)
+      zc = z < l ? l : (z > h ? h : z);
+      if (zc == l && (a == 1 || z < l)) an = 1;
+      else if (zc == h && (a == 2 || z > h)) an = 2;
+    }
+    Un[e] = zc;
+    actn[e] = an;
+  }
+}
+
 }  // namespace
 
 static long long residual_blocks(long long rows) {
@@ -474,6 +512,13 @@ void launch_shift_plan(int model, int N, int M, int sh, const double *X, const d
     hipLaunchKernelGGL((k_shift_plan<Model>), dim3((unsigned)(tail_blocks + cb)), dim3(ROLL_LANES), 0, s, N, M, sh, tail_blocks, X, U, params, U_tail,
                        Xn, Un, um1n);
   });
+}
+void launch_shift_active_set(int N, int M, int u, int Nc, int sh, const double *U, const double *U_tail, const int *act, const double *lo,
+                             const double *hi, double *Un, int *actn, hipStream_t s) {
+  const long long n = (long long)M * N * u;
+  long long b = (n + 255) / 256;
+  if (b > 8192) b = 8192;
+  hipLaunchKernelGGL(k_shift_active_set, dim3((unsigned)b), dim3(256), 0, s, N, u, Nc < 0 || Nc > N ? N : Nc, sh, n, U, U_tail, act, lo, hi, Un, actn);
 }
 bool model_known(int model) { return model >= 0 && model <= 2; }
 bool jac_compact_dims(int model, int x, int u) {

@@ -414,6 +414,9 @@ void launch_linearize_compact(int model, int N, int M, const double *x0, const d
 void launch_rollout(int model, int N, int M, const double *x0, const double *U, const double *params, double *X, hipStream_t s);
 void launch_shift_plan(int model, int N, int M, int sh, const double *X, const double *U, const double *params, const double *U_tail, double *Xn,
                        double *Un, double *um1n, hipStream_t s);
+// control-box statuses moved along with the plan's controls, out of place (include/pmpc_abi.h: pmpc_shift_active_set_device)
+void launch_shift_active_set(int N, int M, int u, int Nc, int sh, const double *U, const double *U_tail, const int *act, const double *lo,
+                             const double *hi, double *Un, int *actn, hipStream_t s);
 bool model_known(int model);                              // a built-in model id (include/pmpc_abi.h)
 bool jac_compact_dims(int model, int x, int u);           // the model has compact records and (x, u) are its dimensions
 long long jac_compact_doubles(int model, int N, int M);  // size of jc (-1: unknown model)

@@ -376,7 +376,7 @@ void pmpc_destroy(pmpc_ctx *c) {
                    &w.warm_lux, &w.Hadd, &w.wu_soc, &w.soc_zl, &w.soc_zu, &w.soc_zc, &w.soc_dzl, &w.soc_dzu, &w.soc_dzc, &w.soc_sl, &w.soc_su, &w.soc_sc, &w.soc_dsl,
                    &w.soc_dsu, &w.soc_dsc, &w.soc_cl, &w.soc_cu, &w.soc_cc, &w.soc_wU, &w.soc_wzl, &w.soc_wzu, &w.soc_wzc, &w.as_act, &w.as_cnt, &w.as_cntp, &w.as_settled, &w.cons_lo, &w.cons_hi, &w.as_ctl, &w.as_delta, &w.as_viol, &w.as_ck, &w.as_jhi, &w.ck_stat, &w.Hc_grp, &w.as_T, &w.xb_qmax, &w.as_perm,
                    &w.sa_f, &w.sa_fx, &w.sa_fu, &w.sa_Xp, &w.sa_Up, &w.sa_Q, &w.sa_R, &w.sa_Xr, &w.sa_Ur, &w.sa_lo, &w.sa_hi, &w.sa_Xo, &w.sa_Uo,
-                   &w.sa_cl, &w.sa_ch, &w.cone_A, &w.cone_c, &w.cone_z, &w.cone_rec, &w.cone_uraw, &w.as_open, &w.xb_z, &w.xb_st, &w.xb_D, &w.xb_g, &w.m64[0], &w.m64[1], &w.m64[2], &w.m64[3], &w.cost_ref[0], &w.cost_ref[1], &w.cost_bad};
+                   &w.sa_cl, &w.sa_ch, &w.cone_A, &w.cone_c, &w.cone_z, &w.cone_rec, &w.cone_uraw, &w.as_open, &w.xb_z, &w.xb_st, &w.xb_D, &w.xb_g, &w.m64[0], &w.m64[1], &w.m64[2], &w.m64[3], &w.cost_ref[0], &w.cost_ref[1], &w.cost_bad, &w.as_act2};
   for (DevBuf *b : all) b->release();
   for (SlabBufs *sb : {&w.sx, &w.su})
     for (DevBuf *b : {&sb->lo, &sb->hi, &sb->tl, &sb->tu, &sb->ll, &sb->lu, &sb->cl, &sb->cu, &sb->D, &sb->w}) b->release();
@@ -550,6 +550,56 @@ int pmpc_shift_plan_device(pmpc_ctx *c, int model, size_t N, size_t M, size_t s,
     HIP_CHECK(hipSetDevice(c->device));
     launch_shift_plan(model, (int)N, (int)M, (int)s, X, U, params, U_tail, X_new, U_new, um1_new, c->stream);
     HIP_CHECK(hipGetLastError());
+  } catch (const PmpcHipError &) {
+    return 1;
+  }
+  return 0;
+}
+
+// The control-box statuses of a plan moved along with its controls (dynamics.hip, k_shift_active_set): on the caller's arrays, and on
+// the set the context's last accepted solve stored — what lets the first solve after a plan shift start like every later one of an SCP
+// loop (pmpc_scp_loop_device with first_cold = 0).
+static bool shift_set_args_ok(const pmpc_ctx *c, size_t N, size_t M, size_t udim, size_t s, const double *U, const double *U_new) {
+  return c && N > 0 && M > 0 && udim > 0 && s >= 1 && s < N && U && U_new && U_new != U && M * N * udim < ((size_t)1 << 40) && N * udim < ((size_t)1 << 30);
+}
+int pmpc_shift_active_set_device(pmpc_ctx *c, size_t N, size_t M, size_t udim, long long Nc, size_t s, const double *U, const double *U_tail, const int *act,
+                                 const double *lo, const double *hi, double *U_new, int *act_new) {
+  if (!shift_set_args_ok(c, N, M, udim, s, U, U_new) || !act || !act_new || act_new == act) return 2;
+  try {
+    HIP_CHECK(hipSetDevice(c->device));
+    launch_shift_active_set((int)N, (int)M, (int)udim, Nc < 0 || Nc > (long long)N ? (int)N : (int)Nc, (int)s, U, U_tail, act, lo, hi, U_new, act_new, c->stream);
+    HIP_CHECK(hipGetLastError());
+  } catch (const PmpcHipError &) {
+    return 1;
+  }
+  return 0;
+}
+int pmpc_warm_shift_device(pmpc_ctx *c, size_t N, size_t M, size_t udim, long long Nc, size_t s, const double *U, const double *U_tail, const double *lo,
+                           const double *hi, double *U_new, int *shifted) {
+  if (!shift_set_args_ok(c, N, M, udim, s, U, U_new) || !shifted) return 2;
+  Workspace &w = c->ws;
+  *shifted = 0;
+  const size_t n = M * N * udim, bytes = n * sizeof(int) + 8;  // (+ 8: the sweeps read the last status as 8 bytes)
+  // (a sharded context's shared controls follow global particle 0, which this rank may not hold: its first solve stays cold)
+  if (w.as_key == -1 || w.as_count != n || w.as_act.bytes < bytes || c->multi()) return 0;
+  try {
+    HIP_CHECK(hipSetDevice(c->device));
+    if (w.as_act2.ensure(w.as_act.bytes)) HIP_CHECK(hipMemsetAsync(w.as_act2.p, 0, w.as_act2.bytes, c->stream));
+    launch_shift_active_set((int)N, (int)M, (int)udim, Nc < 0 || Nc > (long long)N ? (int)N : (int)Nc, (int)s, U, U_tail, (const int *)w.as_act.p, lo, hi, U_new,
+                            (int *)w.as_act2.p, c->stream);
+    HIP_CHECK(hipGetLastError());
+    std::swap(w.as_act, w.as_act2);  // (same size: the solve's own ensure() finds its buffer as large as before)
+    *shifted = 1;
+  } catch (const PmpcHipError &) {
+    return 1;
+  }
+  return 0;
+}
+int pmpc_warm_set_read_device(pmpc_ctx *c, int *act_out, size_t n) {
+  if (!c || !act_out || c->ws.as_key == -1 || c->ws.as_count != n || c->ws.as_act.bytes < n * sizeof(int)) return 2;
+  try {
+    HIP_CHECK(hipSetDevice(c->device));
+    HIP_CHECK(hipMemcpyAsync(act_out, c->ws.as_act.p, n * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
   } catch (const PmpcHipError &) {
     return 1;
   }

@@ -92,6 +92,8 @@ struct Workspace {
   int xb_warm_backoff = 0, xb_warm_fails = 0;  // state rows: solves left for which the warm start is not tried / its failures in a row
   long long as_key = -1;  // shape whose accepted active set (as_act) and solution (U) can start the next solve
   double as_scale = 1.0;
+  size_t as_count = 0;  // statuses of the stored set (M N udim of the solve that set as_key)
+  DevBuf as_act2;  // pmpc_warm_shift_device: the stored set moved along with the plan is written here, then the two buffers are swapped
   DevBuf part_dev;  // barrier mode: block partials of the centrality deviation
   DevBuf sa_f, sa_fx, sa_fu, sa_Xp, sa_Up, sa_Q, sa_R, sa_Xr, sa_Ur, sa_lo, sa_hi, sa_Xo, sa_Uo, sa_cl, sa_ch;  // slew: increment form
   SlabBufs sx, su;

@@ -1082,6 +1082,7 @@ int QpSolve::as_accept(AsAttempt &t) {
   outputs_written = true;
   w.as_key = as_key;  // the stored set (+ w.U) start the next solve of this shape
   w.as_scale = dual_scale;
+  w.as_count = nu;
   if (mode == 0) w.as_pred_rounds = round;
   c->spec_ok = n_batches_at_hook == 1 && !(has_xb && !xbox);  // (with state boxes ignored, a second phase follows)  // what was enqueued behind the first batch saw the final outputs
   return 0;
@@ -1157,6 +1158,7 @@ int QpSolve::active_set_solve(double dual_scale, int mode, int max_rounds, int x
       outputs_written = true;
       w.as_key = as_key;  // act + w.U start the next solve of this shape
       w.as_scale = dual_scale;
+      w.as_count = nu;
       return 0;
     }
     if (changes * 2 > last_changes && ++stalls >= 2) return 1;  // not contracting: leave it to the interior-point iteration

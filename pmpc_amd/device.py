@@ -263,6 +263,63 @@ class DeviceSolver:
             raise RuntimeError(f"pmpc_shift_plan_device failed ({st}): model {model} is not a built-in model, or a HIP error")
         return X_out, U_out, um1_out
 
+    def _shift_set_args(self, what, U, s, U_tail, lo, hi, U_out):
+        M, N, u = U.shape
+        assert (U_tail is None or U_tail.shape == (M, int(s), u)) and (lo is None or lo.shape == U.shape) and (hi is None or hi.shape == U.shape), U.shape
+        U_out = torch.empty_like(U) if U_out is None else U_out
+        assert U_out.shape == U.shape
+        if not 1 <= int(s) < N or U_out.data_ptr() == U.data_ptr():
+            raise ValueError(f"{what}: s = {s} must be in 1 .. N - 1 = {N - 1}, and the shift is not done in place")
+        return M, N, u, U_out
+
+    def shift_active_set(self, act, U, lo, hi, Nc, s=1, U_tail=None, U_out=None, act_out=None, wait_current_stream=True):
+        """Control-box statuses `act` (M, N, u) int32 (0 free, 1 lower, 2 upper bound) moved `s` stages on together with the controls U
+        into the boxes lo / hi (M, N, u; None: unbounded) of the stages they arrive at (pmpc_amd.dynamics.shift_active_set is the
+        specification), one launch on the caller's tensors: returns (act', U').  Never in place."""
+        self._need("pmpc_shift_active_set_device")
+        M, N, u, U_out = self._shift_set_args("shift_active_set", U, s, U_tail, lo, hi, U_out)
+        act_out = torch.empty_like(act) if act_out is None else act_out
+        assert act.shape == U.shape and act_out.shape == U.shape
+        if act_out.data_ptr() == act.data_ptr():
+            raise ValueError("shift_active_set: the shift is not done in place")
+        self._before(wait_current_stream)
+        st = self.lib.pmpc_shift_active_set_device(self.h, N, M, u, int(Nc), int(s), _p(U), _p(U_tail), _p(act, torch.int32), _p(lo), _p(hi), _p(U_out),
+                                                   _p(act_out, torch.int32))
+        self._after(wait_current_stream)
+        if st != 0:
+            raise RuntimeError(f"pmpc_shift_active_set_device failed ({st})")
+        return act_out, U_out
+
+    def warm_shift(self, U, lo, hi, Nc, s=1, U_tail=None, U_out=None, wait_current_stream=True) -> bool:
+        """`shift_active_set` applied to the set this context's last accepted solve stored: U (M, N, u) is the plan BEFORE its shift,
+        `U_out` the shifted plan's controls (written behind `shift_plan` on the solver's stream), lo / hi the problem's lu / uu.  True: the
+        stored statuses now belong to `U_out` and the next `scp_loop` of this shape may run with `first_cold=False`.  False: nothing was
+        stored (no accepted active-set solve of this shape since; a sharded context), nothing ran and `U_out` is untouched.  Stage-cone,
+        state-row and epigraph multipliers are not moved: a problem with those keeps `first_cold=True`."""
+        self._need("pmpc_warm_shift_device")
+        M, N, u, U_out = self._shift_set_args("warm_shift", U, s, U_tail, lo, hi, U_out)
+        shifted = ctypes.c_int(0)
+        self._before(wait_current_stream)
+        st = self.lib.pmpc_warm_shift_device(self.h, N, M, u, int(Nc), int(s), _p(U), _p(U_tail), _p(lo), _p(hi), _p(U_out), ctypes.byref(shifted))
+        self._after(wait_current_stream)
+        if st != 0:
+            raise RuntimeError(f"pmpc_warm_shift_device failed ({st})")
+        return bool(shifted.value)
+
+    def warm_set(self, M, N, u, device=None):
+        """The control-box statuses the last accepted solve stored, an (M, N, u) int32 tensor (a copy), or None if nothing of that size is
+        stored.  For tests and tools."""
+        self._need("pmpc_warm_set_read_device")
+        out = torch.empty((M, N, u), dtype=torch.int32, device=torch.device("cuda", self.device) if device is None else device)
+        self._before()
+        st = self.lib.pmpc_warm_set_read_device(self.h, _p(out, torch.int32), M * N * u)
+        self._after()
+        if st == 2:
+            return None
+        if st != 0:
+            raise RuntimeError(f"pmpc_warm_set_read_device failed ({st})")
+        return out
+
     def linearize_compact(self, model: int, x0, X_prev, U_prev, params, wait_current_stream=True):
         """f (dense) and the compact Jacobian records (one flat tensor) the SCP loop writes for its warm solves."""
         M, N, x = X_prev.shape

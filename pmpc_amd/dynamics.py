@@ -279,6 +279,40 @@ def shift_plan(model, X, U, params, s=1, U_tail=None):
     return Xn, Un, U[:, s - 1].copy()
 
 
+def shift_active_set(act, U, lo, hi, Nc, s, U_tail=None):
+    """The control-box statuses `act` (M, N, u) int32 (0 free, 1 on the lower, 2 on the upper bound) of the plan's controls U moved `s`
+    stages on together with them, 1 <= s < N, into the boxes lo / hi (M, N, u; None: -inf / +inf) of the stages they arrive at — the
+    boxes do not move with the horizon: (act', U') (specification of csrc/dynamics.hip k_shift_active_set).  Entry (i, j, r) takes the
+    control z and the status a of stage j + s (j >= N - s: of `U_tail` (M, s, u) with a = 0; None: of stage N - 1, hold); on a consensus
+    stage j < Nc (Nc < 0: N) every particle takes particle 0's source and particle 0's box, as the solver does.  z is clamped into
+    [l, h]; the status stays where the control is still on that bound, a control the clamp moved is held on the bound it was moved to,
+    everything else is free.  An empty box (l > h) or a NaN control passes through with status 0: the solve's own check refuses it.
+    U' is then bitwise the base point of act' — l where 1, h where 2, inside the box where 0 — and uniform over the particles on the
+    consensus stages: what the first round of the solver's no-rollout warm start verifies of its start iterate."""
+    act, U = np.asarray(act, np.int32), np.asarray(U, float)
+    M, N, u = U.shape
+    if not 1 <= int(s) < N:
+        raise ValueError(f"shift_active_set: s = {s} is outside 1 .. N - 1 = {N - 1}")
+    s = int(s)
+    if act.shape != U.shape:
+        raise ValueError(f"shift_active_set: act {act.shape} and U {U.shape} differ in shape")
+    lo = np.full(U.shape, -np.inf) if lo is None else np.broadcast_to(np.asarray(lo, float), U.shape)
+    hi = np.full(U.shape, np.inf) if hi is None else np.broadcast_to(np.asarray(hi, float), U.shape)
+    Nc = N if Nc < 0 else min(int(Nc), N)
+    if U_tail is None:
+        z, a = np.concatenate([U[:, s:], np.repeat(U[:, N - 1:], s, 1)], 1), np.concatenate([act[:, s:], np.repeat(act[:, N - 1:], s, 1)], 1)
+    else:
+        z = np.concatenate([U[:, s:], np.asarray(U_tail, float).reshape(M, s, u)], 1)
+        a = np.concatenate([act[:, s:], np.zeros((M, s, u), np.int32)], 1)
+    l, h = lo.copy(), hi.copy()
+    z[:, :Nc], a[:, :Nc], l[:, :Nc], h[:, :Nc] = z[:1, :Nc], a[:1, :Nc], lo[:1, :Nc], hi[:1, :Nc]
+    with np.errstate(invalid="ignore"):
+        zc = np.where(z < l, l, np.where(z > h, h, z))  # (not min / max: a signed zero comes out as the kernel's comparisons leave it)
+        an = np.where((zc == l) & ((a == 1) | (z < l)), 1, np.where((zc == h) & ((a == 2) | (z > h)), 2, 0)).astype(np.int32)
+        through = (l > h) | np.isnan(z)
+    return np.where(through, 0, an).astype(np.int32), np.where(through, z, zc)
+
+
 # -------------------------------------------------------------------------------------------------
 # built-in obstacle cost (include/pmpc_abi.h pmpc_scp_cost; NOT in the reference, whose lin_cost_fn is a user callback)
 # -------------------------------------------------------------------------------------------------

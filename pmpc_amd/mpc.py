@@ -9,9 +9,23 @@ The constructor uploads the problem once and allocates every buffer of the libra
 bench.py times); a step is one copy of `x0`, one launch of the plan shift (`DeviceSolver.shift_plan`) and one call of the loop — the
 host reads the per-iteration statuses, the residuals and the first control, nothing else crosses PCIe.
 
-Every step's first SCP iteration runs with `first_cold=True`: after a shift the start iterate is not the previous solve's output, so the
-no-rollout warm start and the compact Jacobian records begin at the second iteration of each step.  (Shifting the solver's active-set
-memory along with the plan is not done.)
+By default every step's first SCP iteration runs with `first_cold=True`: after a shift the start iterate is not the previous solve's
+output, so the no-rollout warm start and the compact Jacobian records begin at the second iteration of each step.
+
+`warm_shift=True` moves the solver's active-set memory along with the plan: behind the plan shift one more launch
+(`DeviceSolver.warm_shift`, specification `pmpc_amd.dynamics.shift_active_set`) moves the control-box statuses the previous step's last
+solve settled on `shift` stages on, clamps the shifted controls into the boxes of the stages they arrive at (`u_l` / `u_u` do not move
+with the horizon) and drops the statuses the new boxes no longer support.  The step's first iteration then runs with `first_cold=False`
+and takes the path of the later ones (warm active-set rounds without a rollout, compact Jacobian records, the follow-up enqueued
+ahead); `info["warm_shift"]` says whether it did — not on the first step after `reset`, and not after a step whose last solve ended
+without an accepted active set (nothing is stored then).  One semantic difference to the default: on the consensus stages (`j < Nc`) the
+start iterate, and with it the linearisation point, holds particle 0's shifted control in every particle, clamped into stage j's box
+(the solver's shared control has one base value); everywhere else the start controls are the shifted plan's, clamped.  Shifted are the
+control-box statuses and the plan's controls only.  The multiplier memories of the stage cones (`cone_z`), the state rows (`xb_z` /
+`xb_st`) and the cone objective's epigraph rows are not, so `warm_shift=True` is refused next to the cone objective (`solver` other than
+the QP path, `smooth_alpha`), `soc=` / `extra_cstrs`, state boxes `x_l` / `x_u`, slew (`slew_rate`, `slew_reg`; their increment form
+restates the controls as states) and `keepout=` (its loop clears the promise the warm start rests on anyway).  `builtin_cost=` is
+allowed; without control boxes nothing is stored and every step stays cold.
 
 `keepout=dict(pos_idx=, centres=, radius=)` is the hard keep-out constraint of `solve(..., device=..., builtin_cstr=...)` (1 to 4 balls in the
 position sub-space `pos_idx`; centres `(K, pos_dim)`, `(N, K, pos_dim)` per stage or `(M, N, K, pos_dim)` per particle and stage) carried
@@ -39,11 +53,33 @@ from .dynamics import model_id
 _SETTINGS = ("solver", "Nc", "smooth_alpha", "slew_reg", "extra_cstrs", "soc_u_interior")
 
 
+def _refuse_with_warm_shift(settings, soc, x_l, x_u, slew_rate, keepout):
+    """`warm_shift=True` moves the control-box statuses and the plan's controls and nothing else: refused next to every feature whose
+    solve carries a warm-start memory of its own that stays at the old stages (or that ends the warm first iteration anyway)."""
+    from .device_problem import _CONE_SOLVERS
+
+    has = lambda z: z is not None and (z.numel() if torch.is_tensor(z) else np.size(z)) > 0
+    why = None
+    if str(settings.get("solver", "ecos")).lower() in _CONE_SOLVERS or "smooth_alpha" in settings or "smooth_cstr" in settings:
+        why = ("the cone objective (solver_settings['solver'] is not the QP path's, e.g. 'osqp', or smooth_alpha is set): the multipliers of "
+               "its epigraph rows are not shifted")
+    elif soc is not None or settings.get("extra_cstrs"):
+        why = "a stage cone (soc= / extra_cstrs): the cones' multiplier memory (cone_z) is not shifted"
+    elif has(x_l) and has(x_u):
+        why = "state boxes x_l / x_u: the state rows' statuses and multipliers (xb_st, xb_z) are not shifted"
+    elif (slew_rate is not None and float(slew_rate) != 0.0) or "slew_reg" in settings:
+        why = "slew penalties (slew_rate, slew_reg): their increment form restates the controls as states, whose rows are not shifted"
+    elif keepout is not None:
+        why = "keepout=: its rows are state rows (not shifted), and the keep-out loop runs no sub-problem as a no-rollout warm start"
+    if why is not None:
+        raise ValueError(f"MPCController: warm_shift=True is not supported next to {why}")
+
+
 class MPCController:
     def __init__(self, builtin_model=None, params=None, Q=None, R=None, X_ref=None, U_ref=None, u_l=None, u_u=None, x_l=None, x_u=None,
                  reg_x: float = 1e0, reg_u: float = 1e-2, solver_settings: Optional[Dict[str, Any]] = None, builtin_cost: Optional[Dict[str, Any]] = None,
                  slew_rate: Optional[float] = None, u0_slew=None, soc: Optional[Dict[str, Any]] = None, device="cuda",
-                 solver: Optional[DeviceSolver] = None, keepout: Optional[Dict[str, Any]] = None, **unsupported):
+                 solver: Optional[DeviceSolver] = None, keepout: Optional[Dict[str, Any]] = None, warm_shift: bool = False, **unsupported):
         if builtin_model is None:
             raise ValueError("MPCController needs builtin_model=: a Python f_fx_fu_fn cannot enter the library's SCP loop")
         if unsupported.get("builtin_cstr") is not None:
@@ -53,6 +89,9 @@ class MPCController:
         if bad:
             raise ValueError(f"MPCController does not support {sorted(bad)}; the host loop pmpc_amd.solve(...) has the host-only features")
         settings = dict(solver_settings or {})
+        if warm_shift:  # what the shifted memory does not cover: before any device is touched
+            _refuse_with_warm_shift(settings, soc, x_l, x_u, slew_rate, keepout)
+        self.warm_shift = bool(warm_shift)
         if keepout is not None:  # what the constraint is refused with, for scp_device.py's reasons: before any device is touched
             from .scp_device import _refuse_with_cstr
 
@@ -177,7 +216,8 @@ class MPCController:
     # ---- one MPC step ----------------------------------------------------------------------------------------
     def step(self, x0, iterations: int = 3, shift: int = 1, U_tail=None, return_torch: bool = False):
         """x0 (x,) or (M, x), numpy or GPU tensor -> (u0, info): u0 = U[:, 0, :] of the new plan, a copy (M, u) (numpy unless
-        `return_torch`); info = dict(resid=per-iteration SCP residuals, infos=per-iteration solver infos, status=, iterations_done=).
+        `return_torch`); info = dict(resid=per-iteration SCP residuals, infos=per-iteration solver infos, status=, iterations_done=,
+        warm_shift=whether the first iteration was started warm from the shifted active set).
         On every call but the first after `reset` the previous plan is first moved `shift` stages on (`U_tail` (M, shift, u): the new
         last controls, None: hold).  A failed sub-problem returns (None, info); the controller then refuses `step` until `reset()`."""
         if self.failed:
@@ -194,6 +234,7 @@ class MPCController:
                 self._aug["x0"][:, :self.xdim].copy_(self._x0)
             if U_tail is not None:
                 U_tail = torch.as_tensor(np.asarray(U_tail) if not torch.is_tensor(U_tail) else U_tail, dtype=torch.float64).to(self.device).contiguous()
+        warm = False
         if self._fresh:
             if self._rollout:
                 s.rollout(self.model, self._x0, self.U, self.params, out=self.X, wait_current_stream=False)
@@ -201,6 +242,8 @@ class MPCController:
             Xn, Un = self._pairs[self._cur ^ 1]
             s.shift_plan(self.model, self.X, self.U, self.params, s=shift, U_tail=U_tail, X_out=Xn, U_out=Un, um1_out=self._um1,
                          wait_current_stream=False)
+            if self.warm_shift:  # the stored statuses follow the plan; the new pair's controls become their base point
+                warm = s.warm_shift(self.U, self._kw["lu"], self._kw["uu"], self._kw["Nc"], s=shift, U_tail=U_tail, U_out=Un, wait_current_stream=False)
             self._cur ^= 1
             self._um1_valid = self._um1 is not None
         self._fresh = False
@@ -208,7 +251,7 @@ class MPCController:
         (Xa, Ua), (Xb, Ub) = self._pairs[self._cur], self._pairs[self._cur ^ 1]
         f, fx, fu, f2, fx2, fu2 = self._lin
         res, infos, last_in_out, done = s.scp_loop(self.model, self.params, iterations, f=f, fx=fx, fu=fu, f2=f2, fx2=fx2, fu2=fu2, X_prev=Xa, U_prev=Ua,
-                                                   X_out=Xb, U_out=Ub, first_cold=True, res=self._res[:iterations], cost=self._cost,
+                                                   X_out=Xb, U_out=Ub, first_cold=not warm, res=self._res[:iterations], cost=self._cost,
                                                    cstr=self._cstr, aug=self._aug, wait_current_stream=False, **slew0, **self._kw)
         if last_in_out:
             self._cur ^= 1
@@ -217,7 +260,7 @@ class MPCController:
             resid = res[:done].cpu().numpy()  # (synchronises the solver's stream)
             u0 = self.U[:, 0, :].clone() if ok else None
         s._after()
-        info = dict(resid=resid, infos=infos, status=0 if ok else int(infos[-1]["status"]), iterations_done=int(done))
+        info = dict(resid=resid, infos=infos, status=0 if ok else int(infos[-1]["status"]), iterations_done=int(done), warm_shift=warm)
         if not ok:
             self.failed = True
             return None, info

@@ -5,6 +5,7 @@ solver (bench.py is); the numbers of CHANGELOG.md's MPCController entry come fro
 
     python tools/mpc_step_time.py --model quadrotor --M 4096 --N 50 --steps 50 --iterations 3
     python tools/mpc_step_time.py --model bicycle --keepout 2        # both versions with a keep-out constraint of 2 balls per particle
+    python tools/mpc_step_time.py --model bicycle --iterations 1 --warm-shift --no-solve   # MPCController(warm_shift=True): the same episode
 
 Kernel times: HIP events on the solver's stream around single launches, all shapes warmed first, the kernels alternating in one loop.
 Step times: host clock around calls that end with a device->host read (both are synchronous), the two versions alternating step by step
@@ -26,7 +27,7 @@ def _stats(v):
 
 
 def kernel_times(solver, mid, d, reps=30):
-    """Median / spread in microseconds of one launch of rollout, shift_plan (s = 1) and linearize."""
+    """Median / spread in microseconds of one launch of rollout, shift_plan (s = 1), linearize and shift_active_set (s = 1)."""
     import torch
 
     X, U = d["X_prev"], d["U_prev"]
@@ -35,6 +36,9 @@ def kernel_times(solver, mid, d, reps=30):
     jobs = {"rollout": lambda: solver.rollout(mid, d["x0"], U, d["params"], out=Xo, wait_current_stream=False)}
     jobs["shift_plan"] = lambda: solver.shift_plan(mid, X, U, d["params"], s=1, X_out=Xo, U_out=Uo, um1_out=um1, wait_current_stream=False)
     jobs["linearize"] = lambda: solver.linearize(mid, d["x0"], X, U, d["params"], f, fx, fu, wait_current_stream=False)
+    if hasattr(solver.lib, "pmpc_shift_active_set_device") and d.get("lu") is not None:  # (an older library under A/B has none)
+        act, act_o = torch.zeros(U.shape, dtype=torch.int32, device=U.device), torch.empty(U.shape, dtype=torch.int32, device=U.device)
+        jobs["shift_active_set"] = lambda: solver.shift_active_set(act, U, d["lu"], d["uu"], 1, s=1, U_out=Uo, act_out=act_o, wait_current_stream=False)
     out = {k: [] for k in jobs}
     with torch.cuda.stream(solver.stream):
         for rep in range(reps + 5):
@@ -59,6 +63,8 @@ def main():
     ap.add_argument("--iterations", type=int, default=3)
     ap.add_argument("--keepout", type=int, default=0, metavar="K", help="K balls per particle beside the start plan (tools/keepout_time.py make_cstr): "
                     "MPCController(keepout=...) against solve(builtin_cstr=...)")
+    ap.add_argument("--warm-shift", action="store_true", help="MPCController(warm_shift=True): the active set is moved along with the plan and the first "
+                    "iteration of a shifted step starts warm; the same episode otherwise")
     ap.add_argument("--no-solve", action="store_true", help="leave the pmpc_amd.solve version out (kernel times and the controller only)")
     args = ap.parse_args()
 
@@ -82,12 +88,15 @@ def main():
         cstr = make_cstr(prob, args.keepout, 3 if args.model == "quadrotor" else 2)
         ctl_kw, solve_kw = dict(keepout={k: cstr[k] for k in ("pos_idx", "centres", "radius")}), dict(builtin_cstr=cstr)
         result["keepout"] = args.keepout
+    if args.warm_shift:
+        ctl_kw["warm_shift"] = True
+    result["warm_shift"] = bool(args.warm_shift)
     ctl = pmpc_amd.MPCController(builtin_model=args.model, params=prob["params"], Q=prob["Q"], R=prob["R"], solver=solver, **ctl_kw, **common)
     ctl.reset(X_prev=prob["X_prev"], U_prev=prob["U_prev"])
     Xs, Us = prob["X_prev"], prob["U_prev"]  # the solve version's warm start
     rng = np.random.default_rng(0)
     x0 = prob["x0"][0]
-    t_ctl, t_solve, first, later = [], [], [], []
+    t_ctl, t_solve, first, later, started_warm = [], [], [], [], []
     fresh, restarts = True, 0  # (fresh: the solve version has no plan to shift)
     for k in range(args.warmup + args.steps):
         t0 = time.perf_counter()
@@ -118,6 +127,7 @@ def main():
             if not args.no_solve:
                 t_solve.append(1e3 * (t3 - t2))
             first.append((info["infos"][0]["active_set_rounds"], info["infos"][0]["ipm_iters"]))
+            started_warm.append(bool(info.get("warm_shift", False)))  # (.get: an older package under A/B has no such entry)
             later += [(i["active_set_rounds"], i["ipm_iters"]) for i in info["infos"][1:]]
         # (with a keep-out constraint the plant is the model: a disturbed state can sit where the linearised rows leave no feasible first stage)
         x0 = F(x0, u0[0], prob["params"][0])[0] + (0.0 if args.keepout else 0.01) * rng.standard_normal(x0.shape)
@@ -129,6 +139,11 @@ def main():
     mean = lambda rows, c: float(np.mean([r[c] for r in rows])) if rows else float("nan")
     result["first_iteration"] = dict(active_set_rounds=mean(first, 0), ipm_iters=mean(first, 1))
     result["later_iterations"] = dict(active_set_rounds=mean(later, 0), ipm_iters=mean(later, 1))
+    # per timed step: (ipm_iters, active_set_rounds) of the first iteration; the share of the timed steps whose first iteration the rounds
+    # finished without the interior-point iteration (every timed step follows a shift: the warm-up steps took the one without)
+    result["first_iteration_per_step"] = [(int(r[1]), int(r[0])) for r in first]
+    result["first_iteration_started_warm"] = float(np.mean(started_warm)) if started_warm else float("nan")
+    result["first_iteration_without_ipm"] = float(np.mean([r[1] == 0 for r in first])) if first else float("nan")
     solver.close()
     print(json.dumps(result))
 
