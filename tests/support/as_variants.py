@@ -22,7 +22,7 @@ OK_TOKEN = "AS_VARIANTS_OK"
 KNOB_ENV = ("PMPC_AS_DEEP2_MAXM", "PMPC_AS_DEEP_MAXM", "PMPC_AS_FWD_PF2_MAXM")
 # (deep2_maxm, deep_maxm, fwd_pf2_maxm); "deep" leaves the last two at the library's defaults
 SETTINGS = {"lean": (0, 0, 0), "deep": (0, 3072, 1 << 30)}
-CHILDREN = [("plain", "lean"), ("plain", "deep"), ("cone", "lean"), ("xbox", "lean"), ("f32", "lean")]
+CHILDREN = [("plain", "lean"), ("plain", "deep"), ("cone", "lean"), ("xbox", "lean"), ("f32", "lean"), ("ragged", "lean"), ("ragged", "deep")]
 
 # PMPC_FAST_DIMS of pmpc_amd/csrc/fast_common.h (tests/test_as_variant.py asserts that the library accepts each pair)
 PAIRS = [(12, 4), (12, 3), (12, 2), (10, 4), (10, 2), (9, 4), (9, 3), (8, 4), (8, 2), (7, 3), (6, 4), (6, 3), (6, 2), (5, 3),
@@ -33,7 +33,7 @@ XBOX_PAIRS = [(12, 4), (4, 2), (6, 3), (2, 1), (9, 3), (8, 4)]
 
 # the family's own bits of `flags` (pmpc_amd/_lib.py: AS_SWEEP_FLAGS) next to defect (1) and as_settled_in (2); as_T stays off: the
 # sensitivity records start at as_sens_min_m particles, far above these
-FAMILY_FLAGS = {"plain": [0], "cone": [8 | 32], "xbox": [16], "f32": [4, 4 | 8 | 32]}
+FAMILY_FLAGS = {"plain": [0], "cone": [8 | 32], "xbox": [16], "f32": [4, 4 | 8 | 32], "ragged": [0]}
 
 # Variants of the expected set that no input of these sizes reaches, by name: (family, setting, pair, sweep, variant) -> reason.
 # Must stay empty for the plain family's full sweeps (MODE 0, MODE 1 with and without DEFECT, both forward rings).
@@ -54,6 +54,21 @@ NEEDS_IPM = {
     ((6, 4), 31102, 2): "warm rounds at their limit, then the finish of the interior-point iteration (15 rounds in all); the same under lean and deep",
 }
 
+# The same for the ragged family (boxes of tests/support/ragged_boxes.py: every instantiation reads lo / hi in its own code).  More than
+# 5 % of the family's 300 solves here would be a finding of its own, to be reported and not written down.
+NEEDS_IPM_RAGGED = {
+    ((10, 4), 35030, 2): "offset boxes, 421 of 540 controls on a side: warm rounds at their limit, then 12 interior-point iterations; the same under lean and deep",
+    ((10, 4), 35030, 3): "the same case one step on (423 on a side): 26 interior-point iterations, 7 rounds",
+    ((8, 4), 35071, 3): "all nine stages shared under +-0.02 boxes, 245 of 252 on a side: warm rounds at their limit (10 counted with the finish)",
+    ((6, 4), 35100, 3): "pinned boxes, 537 sides held among 504 controls (a pinned entry counts on both): warm rounds at their limit, finish of the interior-point iteration",
+    ((6, 3), 35110, 2): "offset boxes, 128 of 162 on a side: warm rounds at their limit, 9 interior-point iterations",
+    ((4, 4), 35150, 0): "offset boxes, 215 of 252 on a side: the cold rounds hand over (10 interior-point iterations, 6 rounds)",
+    ((4, 4), 35150, 2): "the same case, warm: 13 interior-point iterations, 7 rounds",
+    ((4, 4), 35150, 3): "the same case, warm: 12 interior-point iterations, 6 rounds",
+    ((4, 3), 35160, 2): "per-entry boxes, 200 of 270 on a side: warm rounds at their limit (15 counted), 9 interior-point iterations",
+}  # 9 of 300 solves (3 %), the same nine under both settings
+RAGGED_KINDS = ("per_entry", "one_sided", "pinned", "offset")
+
 
 def plain_cases(k):
     """(M, N, Nc) of pair number k: every Nc of {0, 1, 3, N}, N in {1, 2, 9} and one of {3, 5} — N = 1: no MAIN stage, 2: jmin on the
@@ -69,6 +84,13 @@ def family_cases(family):
     if family == "plain":
         for k, (x, u) in enumerate(PAIRS):
             out.append(((x, u), [dict(M=M, N=N, Nc=Nc, seed=31000 + 10 * k + c, bu=0.02 if Nc == N else 0.25) for c, (M, N, Nc) in enumerate(plain_cases(k))]))
+    elif family == "ragged":
+        # three of the plain family's shape classes per pair — N = 9 with one shared stage, N = 9 with three or all shared, N = 2 without —
+        # with M as in plain_cases; the kind of box rotates with pair + case, so that every kind meets every shape class
+        for k, (x, u) in enumerate(PAIRS):
+            shapes = [(9, 1), (9, 3 if k % 2 == 0 else 9), (2, 0)]
+            out.append(((x, u), [dict(M=6 + (3 * k + 2 * c) % 11, N=N, Nc=Nc, seed=35000 + 10 * k + c, bu=0.02 if Nc == N else 0.25, kind=RAGGED_KINDS[(k + c) % 4])
+                                 for c, (N, Nc) in enumerate(shapes)]))
     elif family == "cone":  # sized like SOC_CASES of tests/test_cone_gpu.py
         for k, (x, u) in enumerate(CONE_PAIRS):
             shapes = [(4, 6, 0), (5, 8, 1), (6, 5, 2), (4, 6, 6)]
@@ -214,6 +236,11 @@ def run_case(orc, family, x, u, case, dry):
     M, N, Nc = case["M"], case["N"], case["Nc"]
     if family == "xbox":
         args, kw = xbox_problem(rng, orc, M, N, x, u, Nc, case["bu"], pull=case["pull"], margin=case.get("margin", 0.02))
+    elif family == "ragged":
+        from tests.support.ragged_boxes import ragged_boxes
+
+        args, kw = rand_problem(rng, M, N, x, u, None)
+        kw["u_l"], kw["u_u"] = ragged_boxes(rng, M, N, u, case["kind"], case["bu"])[:2]
     else:
         args, kw = rand_problem(rng, M, N, x, u, case["bu"])
     if family == "f32":  # the oracle solves the float-rounded data widened to double: the problem the device solves
@@ -233,7 +260,12 @@ def run_case(orc, family, x, u, case, dry):
         Xo, Uo = _oracle(orc, family, case, args, kw, u)
         # conditions on the inputs (a test must not pass vacuously): a control on its box; a cone active; a state row binding
         assert np.all(np.isfinite(Xo)) and np.all(np.isfinite(Uo)), (family, x, u, case, t)
-        on_box = int(np.sum((Uo <= kw["u_l"] + 1e-9) | (Uo >= kw["u_u"] - 1e-9)))
+        if family == "ragged":  # on a FINITE side of the boxes the joint program sees (particle 0's on the consensus stages)
+            from tests.support.ragged_boxes import effective_boxes, on_side_counts
+
+            on_box = sum(on_side_counts(Uo, *effective_boxes(kw["u_l"], kw["u_u"], Nc))[:2])
+        else:
+            on_box = int(np.sum((Uo <= kw["u_l"] + 1e-9) | (Uo >= kw["u_u"] - 1e-9)))
         assert on_box > 0, ("no control on its box", family, x, u, case, t)
         note = f"ubox {on_box}"
         if case.get("cone"):
@@ -264,7 +296,7 @@ def run_case(orc, family, x, u, case, dry):
             assert info["fast_path"] == 2 and info["ipm_iters"] == 0 and info["active_set_rounds"] >= 1, (family, x, u, case, t, info)
         else:
             assert info["fast_path"] == 1, (family, x, u, case, t, info)
-        if family == "plain" and ((x, u), case["seed"], t) not in NEEDS_IPM:
+        if family in ("plain", "ragged") and ((x, u), case["seed"], t) not in (NEEDS_IPM if family == "plain" else NEEDS_IPM_RAGGED):
             assert info["ipm_iters"] == 0 and info["active_set_rounds"] >= 1, ("not finished by the rounds alone", family, x, u, case, t, info)
         if t >= 2 and info["ipm_iters"] == 0 and info["active_set_rounds"] >= 1:
             by_defect += 1

@@ -27,7 +27,8 @@ def kkt_certificate(x0, f, fx, fu, X_prev, U_prev, Q, R, X_ref, U_ref, reg_x, re
     lo = np.broadcast_to(u_l, U.shape).copy()
     hi = np.broadcast_to(u_u, U.shape).copy()
     lo[:, :Ncc], hi[:, :Ncc] = lo[:1, :Ncc], hi[:1, :Ncc]  # the shared controls take particle 0's bounds (lqp_utils.jl:329-330)
-    scale_u = np.maximum(1.0, np.maximum(np.abs(lo), np.abs(hi)))
+    # (a removed side, +-inf, sets no scale: with it, `lo + tol scale` is NaN and `hi - tol scale` is -inf, every entry "on" its side)
+    scale_u = np.maximum(1.0, np.maximum(np.where(np.isfinite(lo), np.abs(lo), 0.0), np.where(np.isfinite(hi), np.abs(hi), 0.0)))
     res["box"] = max(0.0, float(((lo - U) / scale_u).max()), float(((U - hi) / scale_u).max()))
     # ---- gradient of the cost, costates, reduced gradient ------------------------------------------------------------------------
     gx = np.einsum("mnrt,mnt->mnr", Q, X - X_ref) + reg_x * (X - X_prev)

@@ -151,7 +151,7 @@ def test_expected_set_of_the_gpu_test_agrees_with_the_recorded_table(setting, ro
         return tuple(int(t) for t in GOLDEN["variants"][sweep][string.ascii_letters.index(cell)].split(",")), True, None
 
     checked = 0
-    for family in ("plain", "cone", "xbox", "f32"):
+    for family in ("plain", "cone", "xbox", "f32", "ragged"):
         for (x, u), cases in family_cases(family):
             if [x, u] not in GOLDEN["pairs"]:
                 continue

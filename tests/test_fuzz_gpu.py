@@ -24,6 +24,14 @@ def test_fuzz_parity_qp_path():
     assert m and int(m.group(2)) == 0 and float(m.group(3)) <= 1e-6, last
 
 
+def test_fuzz_parity_ragged_control_boxes():
+    """Boxes drawn per entry — one-sided, pinned, excluding zero, different per particle on the consensus stages — where every other fuzzer
+    draws +-b: QP path, slew and the hard cone objective."""
+    last = _run("fuzz_parity.py", 111, 150, "ragged")[-1]
+    m = re.search(r"(\d+) cases, (\d+) failures, worst rel err ([0-9.e+-]+)", last)
+    assert m and int(m.group(1)) == 150 and int(m.group(2)) == 0 and float(m.group(3)) <= 1e-6, last
+
+
 def test_fuzz_stage_cones():
     last = _run("fuzz_soc.py", 12, 120)[-1]
     m = re.search(r"(\d+) failures, worst rel err ([0-9.e+-]+)", last)

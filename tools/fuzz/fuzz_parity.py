@@ -1,4 +1,8 @@
-"""One-off stress: random problems through c_lqp_solve / c_lcone_solve vs the oracle (run on a GPU box)."""
+"""One-off stress: random problems through c_lqp_solve / c_lcone_solve vs the oracle (run on a GPU box).
+
+    fuzz_parity.py SEED COUNT [ragged]    ragged: control boxes always present and drawn per entry by tests/support/ragged_boxes.py (kind
+                                          "mixed": one-sided, pinned, offset, .. side by side), no state boxes — so no case can be infeasible
+                                          and an oracle that throws counts as a failure"""
 import faulthandler, sys, time, numpy as np
 faulthandler.enable()
 sys.path.insert(0, ".")
@@ -7,6 +11,9 @@ from pmpc_amd import backend
 from tests.support.problems import abi_args, rand_problem
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 100
+ragged = len(sys.argv) > 3 and sys.argv[3] == "ragged"
+if ragged:  # (only this mode needs the generator: the default mode runs with nothing but tests/support/problems.py)
+    from tests.support.ragged_boxes import ragged_boxes
 dims = [(12, 4), (12, 3), (12, 2), (10, 4), (10, 2), (9, 4), (9, 3), (8, 4), (8, 2), (7, 3), (6, 4), (6, 3), (6, 2), (5, 3), (5, 2), (4, 4),
         (4, 3), (4, 2), (4, 1), (3, 3), (3, 2), (3, 1), (2, 2), (2, 1), (1, 1), (9, 5), (13, 2), (11, 4)]
 worst, fails = 0.0, []
@@ -20,7 +27,11 @@ for k in range(n):
     sl = None if rng.random() < 0.7 else 0.5
     sl0 = None if (sl is None or rng.random() < 0.5) else 0.3
     cone = rng.random() < 0.3 and sl is None
+    if ragged:
+        bu, bx = float(rng.choice([0.1, 0.3, 1.0])), None
     args, kw = rand_problem(rng, M, N, x, u, bu, bx, sl, sl0)
+    if ragged:
+        kw["u_l"], kw["u_u"] = ragged_boxes(rng, M, N, u, "mixed", bu)[:2]
     desc = (M, N, x, u, Nc, bu, bx, sl, sl0, cone)
     if '-v' in sys.argv: print(k, desc, flush=True)
     try:
@@ -31,6 +42,11 @@ for k in range(n):
             Xo, Uo = orc.lqp_solve_py(*args, Nc=Nc, **kw)
             X, U = backend.lqp_solve(*abi_args(args, kw, Nc))
     except Exception as e:  # oracle could not solve (infeasible random boxes): skip
+        if ragged:  # (no state boxes: always feasible)
+            fails.append((desc, float("nan")))
+            print("FAIL", desc, type(e).__name__, e)
+            worst = np.inf
+            continue
         print("skip", desc, type(e).__name__)
         continue
     err = max(np.linalg.norm(X - Xo) / max(np.linalg.norm(Xo), 1e-300), np.linalg.norm(U - Uo) / max(np.linalg.norm(Uo), 1.0))
