@@ -354,6 +354,13 @@ int pmpc_jac_live_mask(int model, unsigned char *fx_mask, unsigned char *fu_mask
  * Returns 1 if the variant is compiled for (xdim, udim), 0 if not, -1 if the pair has no active-set sweeps. */
 int pmpc_as_sweep_variant(int sweep, int xdim, int udim, int M, int Nc, unsigned flags, const int *knobs, int *out);
 
+/* Registers and scratch of ONE compiled instantiation of a sweep, as the loaded code object states them (hipFuncGetAttributes: needs a
+ * device, launches nothing) — for the test that keeps the sweeps on their occupancy step (tests/test_as_resources_gpu.py).  sweep and
+ * variant[0..4]: the record pmpc_as_sweep_variant writes to out[0..4].  out[0..3] = {vector registers per lane (the unified file:
+ * architectural + accumulation), scratch ("local") bytes per lane, static LDS bytes, max threads per block}.  Returns 0, -1 for an
+ * unknown sweep or a pair without active-set sweeps, -2 if the variant is not compiled for the pair, else the HIP error code. */
+int pmpc_as_sweep_resources(int sweep, int xdim, int udim, const int *variant, int *out);
+
 /* How often each variant of a sweep has been launched by this process (every context and dims pair together) since it started or
  * since the last call with reset != 0 — host-side counts of the launcher, for tests that must know which instantiations a solve ran
  * (tests/test_as_variants_gpu.py).  The count of a variant stands at the code of its record:

@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "pmpc_scp_residual_device", "pmpc_profile_read_partial", "pmpc_profile_read_all", "pmpc_scp_loop_device", "pmpc_linearize_device_f32",
     "pmpc_set_option", "pmpc_get_option", "pmpc_abi_struct_sizes", "pmpc_lcone_solve_host_ex", "pmpc_restart_stats",
     "pmpc_linearize_compact_device", "pmpc_expand_jac_device", "pmpc_jac_compact_doubles", "pmpc_jac_live_mask",
-    "pmpc_as_sweep_variant", "pmpc_as_sweep_launches", "pmpc_as_sweep_knobs",
+    "pmpc_as_sweep_variant", "pmpc_as_sweep_launches", "pmpc_as_sweep_knobs", "pmpc_as_sweep_resources",
     "pmpc_ref_shift_device", "pmpc_ref_shift_bad_pivots", "pmpc_obstacle_cost_grad_device", "pmpc_obstacle_ref_shift_device",
     "pmpc_scp_loop_device_cost", "pmpc_abi_scp_cost_size",
     "pmpc_rollout_device", "pmpc_shift_plan_device",
@@ -147,6 +147,9 @@ def load():
         lib.pmpc_as_sweep_launches.restype = ctypes.c_int
         lib.pmpc_as_sweep_knobs.argtypes = [ctypes.POINTER(ctypes.c_int)]
         lib.pmpc_as_sweep_knobs.restype = None
+    if hasattr(lib, "pmpc_as_sweep_resources"):  # (likewise)
+        lib.pmpc_as_sweep_resources.argtypes = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+        lib.pmpc_as_sweep_resources.restype = ctypes.c_int
     lib.pmpc_scp_residual_device.argtypes = [vp, sz, sz, sz, sz] + [vp] * 5
     lib.pmpc_scp_residual_device.restype = ctypes.c_int
     lib.pmpc_profile_enable.argtypes = [vp, ctypes.c_int]
@@ -254,6 +257,21 @@ def as_sweep_variant(sweep: str, x: int, u: int, M: int, Nc: int, flags: int, kn
     if got < 0:
         raise ValueError(f"({x}, {u}) is not a compiled pair of the active-set sweeps")
     return tuple(out[:5]), bool(got), tuple(bool(v) for v in out[5:8])
+
+
+def as_sweep_resources(sweep: str, x: int, u: int, variant):
+    """{"regs", "scratch_bytes", "lds_bytes", "max_threads"} of the compiled instantiation `variant` (a record as as_sweep_variant
+    returns it) of the factor ("bwd") / forward ("fwd") sweep for (x, u), from the loaded code object; None if that variant is not
+    compiled for the pair.  Needs a device, launches nothing."""
+    out = (ctypes.c_int * 4)()
+    got = load().pmpc_as_sweep_resources({"bwd": 0, "fwd": 1}[sweep], x, u, (ctypes.c_int * 5)(*(int(v) for v in variant)), out)
+    if got == -2:
+        return None
+    if got == -1:
+        raise ValueError(f"({x}, {u}) is not a compiled pair of the active-set sweeps")
+    if got != 0:
+        raise RuntimeError(f"pmpc_as_sweep_resources: HIP error {got}")
+    return dict(zip(("regs", "scratch_bytes", "lds_bytes", "max_threads"), (int(v) for v in out)))
 
 
 def as_sweep_code(sweep: str, variant) -> int:

@@ -37,6 +37,19 @@ __device__ __forceinline__ double row_allsum(double v) {
   v += dpp_d<0x140>(v);
   return v;
 }
+// out = v of lane C0 + g of the lane's OWN row, for a lane of row (k-group) g < NB; 0 in the rows g >= NB.  One row-masked
+// row_newbcast move per row (the one DPP control gfx950 has in 64-bit form: v_mov_b64_dpp): row g alone takes broadcast g, the
+// other rows keep what they have.  With NB == 4 every row is written and the first move needs no "old" value (no init moves);
+// with fewer rows the chain starts from zero.  All 64 lanes must be enabled (a DPP move reads 0 from a disabled lane).
+template <int C0, int NB>
+__device__ __forceinline__ double row_own_bcast(double v) {
+  static_assert(NB >= 1 && NB <= 4 && C0 >= 0 && C0 + NB <= 16, "row_own_bcast: lanes C0 .. C0 + NB - 1 of a 16-lane row");
+  double o = NB == 4 ? __builtin_amdgcn_update_dpp(0.0, v, 0x150 + C0, 0xF, 0xF, true) : __builtin_amdgcn_update_dpp(0.0, v, 0x150 + C0, 0x1, 0xF, false);
+  if (NB > 1) o = __builtin_amdgcn_update_dpp(o, v, 0x150 + C0 + (NB > 1 ? 1 : 0), 0x2, 0xF, false);
+  if (NB > 2) o = __builtin_amdgcn_update_dpp(o, v, 0x150 + C0 + (NB > 2 ? 2 : 0), 0x4, 0xF, false);
+  if (NB > 3) o = __builtin_amdgcn_update_dpp(o, v, 0x150 + C0 + (NB > 3 ? 3 : 0), 0x8, 0xF, false);
+  return o;
+}
 // Cross-row exchanges on the VALU (gfx950 v_permlane32_swap / v_permlane16_swap; semantics checked on
 // hardware, tools/micro/swap_test): with both operands equal to v,
 //   permlane32_swap -> [0] = v of the lane in rows {0,1} at the same position, [1] = same for rows {2,3}

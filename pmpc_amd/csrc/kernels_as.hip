@@ -77,8 +77,12 @@ namespace {
 // MT: storage type of the matrix stacks fx, fu, Q, R and of the factor record (float = the fp32-storage mode; arithmetic stays fp64).
 // EX = 2, XBOX: state boxes ride along (kernels_xbox.hip prepares their terms per round): a penalty xb_D on the diagonal of the state
 // cost of the stage below and xb_g in its gradient — two more loads per stage, on the state columns, next to the base state's.
+// The deep full DEFECT sweep of the flagship shape runs at 4 waves per SIMD (select_bwd_as relies on it: "never lean with DEFECT"): it
+// sits at the 128-register step, so the allocator gets the occupancy it has to reach as a bound instead of reaching it by luck
+// (tests/test_as_resources_gpu.py holds the line), and its main loop takes two stages per trip.
+#define AS_DEEP_FITS4 (XD == 12 && UD == 4 && DEFECT && !SKIP && EX == 0 && sizeof(MT) == 8)
 template <int XD, int UD, int MODE, bool SKIP, bool DEFECT, int EX = 0, class MT = double>
-__global__ void __launch_bounds__(64, MODE == 2 ? 2 : (MODE == 1 ? PMPC_AS_DEEP_WAVES : PMPC_AS_LEAN_WAVES)) k_bwd_as(LQArgs a) {
+__global__ void __launch_bounds__(64, MODE == 2 ? 2 : (MODE == 1 ? (AS_DEEP_FITS4 ? 4 : PMPC_AS_DEEP_WAVES) : PMPC_AS_LEAN_WAVES)) k_bwd_as(LQArgs a) {
   constexpr bool CONE = EX == 1, XBOX = EX == 2;
   typedef Lane<XD, UD> LT;
   constexpr int KS = LT::KS, XP = LT::XP;
@@ -164,6 +168,9 @@ __global__ void __launch_bounds__(64, MODE == 2 ? 2 : (MODE == 1 ? PMPC_AS_DEEP_
   bool dmask[KS];
 #pragma unroll
   for (int r = 0; r < KS; r++) dmask[r] = diag_x && (c >> 2) == r;
+  int unit_hi[UD];  // high word of the unit right-hand side e_cb of the control columns (1.0 in entry cb, the low word is zero); the lanes behind them: 0
+#pragma unroll
+  for (int k = 0; k < UD; k++) unit_hi[k] = L.cb == k ? 0x3FF00000 : 0;
   // particle-local bases once (scalar registers); per stage only `stage index * block size` is added on the scalar unit
   const long long px = (long long)(pbase * XD) * D8, pu = (long long)(pbase * UD) * D8;
   const double *Xb_ = ubase(Xb, px), *Xr_ = ubase(a.X_ref, px), *Xp_ = ubase(a.X_prev, px), *f_ = ubase(a.f, px);
@@ -356,9 +363,14 @@ __global__ void __launch_bounds__(64, MODE == 2 ? 2 : (MODE == 1 ? PMPC_AS_DEEP_
 #pragma unroll
     for (int r = 0; r < KS; r++) hp = fma(Fr[r], s_row[r], hp);
     const double h_col = grp_allsum(hp);
+    // control rows of h: the general body reads them out lane-uniform (the consensus export needs them by index); a MAIN stage needs
+    // only hu[g] in k-group g and hu[cb] in control column cb — h_col is the same in all four k-groups, so the first is lane XP + g of
+    // the lane's own row (row-masked broadcasts) and the second the lane's own h_col: no readlanes, no select chains
     double hu[UD];
+    if constexpr (!MAIN) {
 #pragma unroll
-    for (int b = 0; b < UD; b++) hu[b] = readlane_d(h_col, XP + b);
+      for (int b = 0; b < UD; b++) hu[b] = readlane_d(h_col, XP + b);
+    }
 
     TL(3);  // gradient h = F' (s + S r) formed, control rows read out
     // ---- H = F' S F + blkdiag(Q~_{j-1}, R~_j) ------------------------------------------------------
@@ -425,7 +437,8 @@ __global__ void __launch_bounds__(64, MODE == 2 ? 2 : (MODE == 1 ? PMPC_AS_DEEP_
     double rows4[4];
     grp_gather(H[KS], rows4);
 #pragma unroll
-    for (int k = 0; k < UD; k++) col[k] = L.cu ? (L.cb == k ? 1.0 : 0.0) : rows4[k];
+    for (int k = 0; k < UD; k++)  // (selected by halves: as doubles the unit vectors sat in 2 UD registers and came in through a branch on exec and UD moves)
+      col[k] = __hiloint2double(c < XP ? __double2hiint(rows4[k]) : unit_hi[k], c < XP ? __double2loint(rows4[k]) : 0);
     chol_solve<UD>(Lc, Ld, col);
     const double Kg = pick<UD>(col, g);
     const double rec = frec ? Kg : 0.0;
@@ -440,8 +453,10 @@ __global__ void __launch_bounds__(64, MODE == 2 ? 2 : (MODE == 1 ? PMPC_AS_DEEP_
     }
     const double Kreg = L.cxv ? rec : 0.0;
     // ---- feed-forward k = Huu^-1 hu: the control quad of k-group g holds row g of Huu^-1 ---------------
-    const double hug = pick<UD>(hu, g);
-    double kq = L.cu ? rec * pick<UD>(hu, L.cb) : 0.0;
+    double hug, huc;
+    if constexpr (MAIN) { hug = row_own_bcast<XP, UD>(h_col); huc = h_col; }  // (rows g >= UD: 0, as pick gives; Kreg is zero there)
+    else { hug = pick<UD>(hu, g); huc = pick<UD>(hu, L.cb); }
+    double kq = L.cu ? rec * huc : 0.0;
     kq += dpp_d<0xB1>(kq);
     kq += dpp_d<0x4E>(kq);
     if (c == XP && gu) gsto(ubase(kff_, uoff(j)), lug, kq);
@@ -489,6 +504,14 @@ __global__ void __launch_bounds__(64, MODE == 2 ? 2 : (MODE == 1 ? PMPC_AS_DEEP_
     Pipe A, B;
     fetch_early(jtop, A);
     fetch_late(jtop, jtop >= 1 ? jtop - 1 : 0, A);
+    if constexpr (AS_DEEP_FITS4) {
+      // two stages per trip, the roles of the two sets static: no A = B moves (8 of a stage's ~250 vector instructions).  Only where it
+      // is known to fit: the scheduler overlaps the two stages, which costs the other deep instantiations of (12, 4) 10 - 16 registers
+      for (; j - 1 >= jmin; j -= 2) {
+        stage(std::true_type{}, j, A, B);
+        stage(std::true_type{}, j - 1, B, A);
+      }
+    }
     for (; j >= jmin; j--) {
       stage(std::true_type{}, j, A, B);
       A = B;
@@ -837,8 +860,11 @@ __global__ void __launch_bounds__(64, 4) k_fwd_as(LQArgs a) {
       for (int r = 1; r < KS; r++) mine = (c == r) ? D[r] : mine;
       gsto(ubase(Xo_, xoff(j)), lx1, cur.xb + mine);
     }
+    // The columns of the tile behind the state (and sensitivity) columns carry nothing and need no mask: a column of the product
+    // depends on the same column of V, bop and the defect alone, all zero there (V starts at zero, bop and dfo are selected to zero
+    // outside c < 4 (+ UD)), and no lane of those columns stores or decides anything.
 #pragma unroll
-    for (int r = 0; r < KS; r++) V[r] = (c < (SENS ? 4 + UD : 4)) ? D[r] : 0.0;  // (the other columns of the tile carry nothing: kept at zero)
+    for (int r = 0; r < KS; r++) V[r] = D[r];
     TL(5);  // new state stored and in place
     TL_FLUSH(j);
   };
@@ -1108,6 +1134,37 @@ int pmpc_as_sweep_variant(int sweep, int xdim, int udim, int M, int Nc, unsigned
   const FwdAsVariant v = select_fwd_as(M, Nc, defect, mat32, as_uraw, as_T, k);
   out[0] = v.defect; out[1] = v.pf2; out[2] = v.cone; out[3] = v.f32; out[4] = v.sens;
   return fwd_as_compiled(v, xdim, udim);
+}
+// Registers and scratch of a compiled instantiation, as the loaded code object states them (include/pmpc_abi.h; tests/test_as_resources_gpu.py).
+namespace {
+template <int XD, int UD>
+int as_sweep_attr_t(int sweep, const int *f, hipFuncAttributes *attr) {
+  int got = -2;  // the variant is not compiled for the pair
+  if (sweep == 0) {
+    if (f[0] < 0 || f[0] > 2 || f[3] < 0 || f[3] > 2) return -2;
+    lift3(f[0], [&](auto MODE) { lift(f[1] != 0, [&](auto SKIP) { lift(f[2] != 0, [&](auto DEFECT) { lift3(f[3], [&](auto EX) { lift(f[4] != 0, [&](auto F32) {
+      if constexpr (bwd_as_compiled(BwdAsVariant{MODE, SKIP, DEFECT, EX, F32}, XD, UD))
+        got = (int)hipFuncGetAttributes(attr, (const void *)&k_bwd_as<XD, UD, MODE, SKIP, DEFECT, EX, std::conditional_t<F32, float, double>>);
+    }); }); }); }); });
+  } else {
+    lift(f[0] != 0, [&](auto DEFECT) { lift(f[1] != 0, [&](auto PF2) { lift(f[2] != 0, [&](auto CONE) { lift(f[3] != 0, [&](auto F32) { lift(f[4] != 0, [&](auto SENS) {
+      if constexpr (fwd_as_compiled(FwdAsVariant{DEFECT, PF2, CONE, F32, SENS}, XD, UD))
+        got = (int)hipFuncGetAttributes(attr, (const void *)&k_fwd_as<XD, UD, DEFECT, PF2, CONE, std::conditional_t<F32, float, double>, SENS>);
+    }); }); }); }); });
+  }
+  return got;
+}
+}  // namespace
+int pmpc_as_sweep_resources(int sweep, int xdim, int udim, const int *variant, int *out) {
+  if ((sweep != 0 && sweep != 1) || !as_dims_compiled(xdim, udim) || !variant || !out) return -1;
+  hipFuncAttributes attr = {};
+  int got = -1;
+#define X(xd, ud) if (xdim == xd && udim == ud) got = as_sweep_attr_t<xd, ud>(sweep, variant, &attr);
+  PMPC_FAST_DIMS(X)
+#undef X
+  if (got != 0) return got;
+  out[0] = attr.numRegs; out[1] = (int)attr.localSizeBytes; out[2] = (int)attr.sharedSizeBytes; out[3] = attr.maxThreadsPerBlock;
+  return 0;
 }
 int pmpc_as_sweep_launches(int sweep, unsigned long long *out, int n, int reset) {
   if (sweep != 0 && sweep != 1) return -1;
