@@ -280,6 +280,30 @@ int pmpc_comm_world(pmpc_ctx *ctx);
 int pmpc_linearize_device(pmpc_ctx *ctx, int model, size_t N, size_t M, const double *x0, const double *X_prev,
                           const double *U_prev, const double *params, double *f, double *fx, double *fu);
 
+/* Custom dynamics models: x+ = F(x, u; p) handed over as device code, compiled at run time with forward-mode automatic
+ * differentiation for the Jacobians.  `source` is one function template,
+ *   template <class T> __device__ void step(const T *x, const T *u, const double *p, T *xn);   // x[XD], u[UD], p[PD] -> xn[XD]
+ * with XD, UD, PD defined as macros in front of it.  T is double (rollout, plan shift) or a dual number (linearisation) with
+ * + - * / (also against double), unary minus, compound assignment, comparisons by value and
+ * sin cos tan exp log sqrt tanh atan atan2 pow(T, double) fabs fmin fmax; at a kink the derivative is that of the value's branch.
+ * The function sees per-thread arrays only.
+ *   pmpc_model_compile  needs no context and no GPU.  arch: the target id, e.g. "gfx950" (a feature suffix after ':' is dropped).
+ *                       0: *code (malloc'd, pmpc_model_free_code) holds *bytes of code object; 1: a bad argument (xdim, udim or pdim
+ *                       outside 1 .. 16 — the solver's limits); 2: the runtime compiler (libhiprtc.so) is not available; 3: a compile
+ *                       error.  log (log_cap bytes, may be NULL) receives the compiler's text, 0-terminated.
+ *   pmpc_model_load     loads a code object on ctx's device and returns its model id >= PMPC_MODEL_CUSTOM0, or a negative value (-1 HIP
+ *                       error, -2 bad argument, -3 not a code object of pmpc_model_compile for these dimensions).  The id is known to
+ *                       this context only, until pmpc_model_unload (0; 2: not an id of this context) or pmpc_destroy.
+ * A loaded id is taken by pmpc_linearize_device, pmpc_rollout_device, pmpc_shift_plan_device and the pmpc_scp_loop_device family
+ * (params (M, pdim); dense fp64 Jacobians: refused like an unknown id next to PMPC_F32_MATRICES, and when xdim / udim are not the
+ * problem's).  pmpc_linearize_device_f32 and the compact-record entry points know built-in ids only. */
+#define PMPC_MODEL_CUSTOM0 1000
+int pmpc_model_compile(const char *source, int xdim, int udim, int pdim, const char *arch, void **code, size_t *bytes, char *log,
+                       size_t log_cap);
+void pmpc_model_free_code(void *code);
+int pmpc_model_load(pmpc_ctx *ctx, const void *code, size_t bytes, int xdim, int udim, int pdim);
+int pmpc_model_unload(pmpc_ctx *ctx, int id);
+
 /* the same with fx / fu written as FLOAT arrays (PMPC_F32_MATRICES) */
 int pmpc_linearize_device_f32(pmpc_ctx *ctx, int model, size_t N, size_t M, const double *x0, const double *X_prev,
                               const double *U_prev, const double *params, double *f, float *fx, float *fu);

@@ -34,7 +34,9 @@ ABI_SYMBOLS = [
     "pmpc_keepout_augment_device", "pmpc_abi_scp_cstr_size",
     "pmpc_keepout_strip_residual_device", "pmpc_scp_loop_device_cstr", "pmpc_abi_scp_aug_size", "pmpc_scp_loop_follow_ups",
     "pmpc_shift_active_set_device", "pmpc_warm_shift_device", "pmpc_warm_set_read_device",
+    "pmpc_model_compile", "pmpc_model_free_code", "pmpc_model_load", "pmpc_model_unload",
 ]
+MODEL_CUSTOM0 = 1000  # PMPC_MODEL_CUSTOM0 (include/pmpc_abi.h): ids from here on are runtime-compiled models loaded on a context
 
 
 class PmpcProblem(ctypes.Structure):
@@ -213,6 +215,15 @@ def load():
         lib.pmpc_warm_shift_device.restype = ctypes.c_int
         lib.pmpc_warm_set_read_device.argtypes = [vp, vp, sz]
         lib.pmpc_warm_set_read_device.restype = ctypes.c_int
+    if hasattr(lib, "pmpc_model_compile"):  # (likewise: runtime-compiled dynamics models)
+        lib.pmpc_model_compile.argtypes = [ctypes.c_char_p] + [ctypes.c_int] * 3 + [ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.c_char_p, sz]
+        lib.pmpc_model_compile.restype = ctypes.c_int
+        lib.pmpc_model_free_code.argtypes = [vp]
+        lib.pmpc_model_free_code.restype = None
+        lib.pmpc_model_load.argtypes = [vp, ctypes.c_char_p, sz] + [ctypes.c_int] * 3
+        lib.pmpc_model_load.restype = ctypes.c_int
+        lib.pmpc_model_unload.argtypes = [vp, ctypes.c_int]
+        lib.pmpc_model_unload.restype = ctypes.c_int
     lib.pmpc_version.argtypes = []
     lib.pmpc_version.restype = ctypes.c_char_p
     # layout check: the library's structs against this binding's mirrors (include/pmpc_abi.h: pmpc_abi_struct_sizes)

@@ -14,6 +14,7 @@
 // thread's own 1152-byte block reached 1.9 TB/s; the staged version is write-bandwidth bound).
 #include "pmpc_dev.h"
 #include "jac_compact.h"
+#include "model_jit.h"
 #include <cstring>
 #include <cstdlib>
 
@@ -480,6 +481,7 @@ static long long residual_blocks(long long rows) {
 
 void launch_linearize(int model, int N, int M, const double *x0, const double *X_prev, const double *U_prev,
                       const double *params, double *f, double *fx, double *fu, hipStream_t s, int jac32) {
+  if (model_custom(model)) return custom_launch_linearize(model, N, M, x0, X_prev, U_prev, params, f, fx, fu, s);  // (fp64 only: the entry points refuse jac32)
   ResArgs none;
   memset(&none, 0, sizeof(none));
   with_model(model, [&](auto m) { launch_model<decltype(m)>(N, M, x0, X_prev, U_prev, params, f, fx, fu, none, s, jac32); });
@@ -498,11 +500,13 @@ void launch_linearize_compact(int model, int N, int M, const double *x0, const d
   with_model(model, [&](auto m) { launch_model_compact<decltype(m)>(N, M, x0, X_prev, U_prev, params, f, jc, r, s); });
 }
 void launch_rollout(int model, int N, int M, const double *x0, const double *U, const double *params, double *X, hipStream_t s) {
+  if (model_custom(model)) return custom_launch_rollout(model, N, M, x0, U, params, X, s);
   const unsigned grid = (unsigned)((M + ROLL_LANES - 1) / ROLL_LANES);
   with_model(model, [&](auto m) { hipLaunchKernelGGL((k_rollout<decltype(m)>), dim3(grid), dim3(ROLL_LANES), 0, s, N, M, x0, U, params, X); });
 }
 void launch_shift_plan(int model, int N, int M, int sh, const double *X, const double *U, const double *params, const double *U_tail, double *Xn,
                        double *Un, double *um1n, hipStream_t s) {
+  if (model_custom(model)) return custom_launch_shift_plan(model, N, M, sh, X, U, params, U_tail, Xn, Un, um1n, s);
   const int tail_blocks = (M + ROLL_LANES - 1) / ROLL_LANES;
   with_model(model, [&](auto m) {
     typedef decltype(m) Model;
@@ -568,6 +572,10 @@ void launch_widen_f32(const float *src, double *dst, long long n, hipStream_t s)
 void launch_linearize_with_residual(int model, int N, int M, const double *x0, const double *X_prev, const double *U_prev,
                                     const double *params, double *f, double *fx, double *fu, const double *Xr, const double *Xrp,
                                     const double *Ur, const double *Urp, int x, int u, double *res_out, hipStream_t s, int jac32) {
+  if (model_custom(model)) {  // a runtime-compiled model has no residual blocks of its own: its linearisation, then the residual kernel
+    custom_launch_linearize(model, N, M, x0, X_prev, U_prev, params, f, fx, fu, s);
+    return launch_scp_residual(Xr, Xrp, Ur, Urp, (long long)M * N, x, u, res_out, s, false);
+  }
   ResArgs r;
   r.X = Xr; r.Xp = Xrp; r.U = Ur; r.Up = Urp; r.rows = (long long)M * N; r.x = x; r.u = u;
   r.nblk = (int)residual_blocks(r.rows);

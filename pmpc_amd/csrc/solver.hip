@@ -14,6 +14,7 @@
 #include "solver_internal.h"
 #include "cost_lin.h"
 #include "keepout.h"
+#include "model_jit.h"
 #include <atomic>
 
 namespace {
@@ -367,6 +368,7 @@ void pmpc_destroy(pmpc_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
+  custom_models_unload_all(c);  // runtime-compiled models loaded on this context (model_jit.hip)
   if (c->comm && c->mock_comm) delete (MockRank *)c->comm;
   else if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   Workspace &w = c->ws;
@@ -507,7 +509,7 @@ int pmpc_linearize_device_f32(pmpc_ctx *c, int model, size_t N, size_t M, const 
                               const double *U_prev, const double *params, double *f, float *fx, float *fu) {
   try {
     HIP_CHECK(hipSetDevice(c->device));
-    if (!model_known(model)) return 2;
+    if (!model_known(model)) return 2;  // (built-in ids only: a runtime-compiled model writes fp64 Jacobians)
     ProfScope ps(c, 6);
     launch_linearize(model, (int)N, (int)M, x0, X_prev, U_prev, params, f, (double *)fx, (double *)fu, c->stream, 1);
     HIP_CHECK(hipGetLastError());
@@ -521,7 +523,7 @@ int pmpc_linearize_device(pmpc_ctx *c, int model, size_t N, size_t M, const doub
                           const double *U_prev, const double *params, double *f, double *fx, double *fu) {
   try {
     HIP_CHECK(hipSetDevice(c->device));
-    if (!model_known(model)) return 2;
+    if (!model_known(c, model)) return 2;
     ProfScope ps(c, 6);
     launch_linearize(model, (int)N, (int)M, x0, X_prev, U_prev, params, f, fx, fu, c->stream);
     HIP_CHECK(hipGetLastError());
@@ -531,9 +533,9 @@ int pmpc_linearize_device(pmpc_ctx *c, int model, size_t N, size_t M, const doub
   return 0;
 }
 
-// Nonlinear rollout and receding-horizon shift of a built-in model (dynamics.hip): asynchronous on the context's stream.
+// Nonlinear rollout and receding-horizon shift of a built-in or runtime-compiled model (dynamics.hip, model_jit.hip): asynchronous on the context's stream.
 int pmpc_rollout_device(pmpc_ctx *c, int model, size_t N, size_t M, const double *x0, const double *U, const double *params, double *X) {
-  if (!c || !model_known(model) || N == 0 || M == 0 || !x0 || !U || !params || !X) return 2;
+  if (!c || !model_known(c, model) || N == 0 || M == 0 || !x0 || !U || !params || !X) return 2;
   try {
     HIP_CHECK(hipSetDevice(c->device));
     launch_rollout(model, (int)N, (int)M, x0, U, params, X, c->stream);
@@ -545,7 +547,7 @@ int pmpc_rollout_device(pmpc_ctx *c, int model, size_t N, size_t M, const double
 }
 int pmpc_shift_plan_device(pmpc_ctx *c, int model, size_t N, size_t M, size_t s, const double *X, const double *U, const double *params,
                            const double *U_tail, double *X_new, double *U_new, double *um1_new) {
-  if (!c || !model_known(model) || N == 0 || M == 0 || s < 1 || s >= N || !X || !U || !params || !X_new || !U_new || X_new == X || U_new == U) return 2;
+  if (!c || !model_known(c, model) || N == 0 || M == 0 || s < 1 || s >= N || !X || !U || !params || !X_new || !U_new || X_new == X || U_new == U) return 2;
   try {
     HIP_CHECK(hipSetDevice(c->device));
     launch_shift_plan(model, (int)N, (int)M, (int)s, X, U, params, U_tail, X_new, U_new, um1_new, c->stream);
@@ -910,7 +912,13 @@ int pmpc_scp_loop_device_cstr(pmpc_ctx *c, int model, const double *params, cons
   //  not solved with: a stage cone, slew penalties, fp32-stored matrices, a sharded context, the squareplus smoothing of the boxes)
   const bool cstr_refused = with_cstr && (!keepout_cstr_valid(cstr, x) || !keepout_strip_dims_valid(p0->xdim, K, p0->udim) || !scp_aug_complete(aug) || soc ||
                                           (p0->flags & (PMPC_HAS_SLEW | PMPC_HAS_SLEW0)) || jac32 || c->multi() || p0->smooth_cstr == 1);
-  if (!model_known(model) || (with_cost && (jac32 || !obstacle_cost_valid(cost, x))) || cstr_refused) {  // nothing runs (the kernels of some other model would read the caller's arrays with ITS dimensions)
+  // (and a runtime-compiled model whose dimensions are not the problem's, or next to fp32-stored matrices: its Jacobians are doubles)
+  bool custom_refused = false;
+  if (model_custom(model)) {
+    int mx = 0, mu = 0;
+    custom_refused = jac32 || !custom_model_dims(model, &mx, &mu) || mx != x || mu != u;
+  }
+  if (!model_known(c, model) || custom_refused || (with_cost && (jac32 || !obstacle_cost_valid(cost, x))) || cstr_refused) {  // nothing runs (the kernels of some other model would read the caller's arrays with ITS dimensions)
     if (infos && steps > 0) { memset(&infos[0], 0, sizeof(pmpc_info)); infos[0].status = 2; }
     if (last_in_out) *last_in_out = 0;
     return 0;

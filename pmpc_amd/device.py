@@ -49,6 +49,40 @@ class DeviceSolver:
         self.stream = torch.cuda.ExternalStream(self.lib.pmpc_stream(h), device=self.device)
         self.rank, self.world = 0, 1
         self.last_info: Dict[str, float] = {}
+        self._custom: Dict[int, object] = {}  # model id -> the CustomModel loaded under it (load_model)
+
+    # ---- runtime-compiled dynamics models (pmpc_amd/custom_model.py) -----------------------------------
+    def load_model(self, cm) -> int:
+        """The model id (>= 1000) of a `pmpc_amd.CustomModel` on this solver: compiled for the device's architecture and loaded on
+        first use, the same id from then on.  `linearize`, `rollout`, `shift_plan` and `scp_loop` take it as they take 0 - 2; it is
+        known to this solver only and goes with `unload_model` or `close`."""
+        self._need("pmpc_model_load")
+        for mid, loaded in self._custom.items():
+            if loaded is cm:
+                return mid
+        arch = torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0]  # the target id alone, never a feature suffix
+        code = cm.compile(arch)
+        mid = self.lib.pmpc_model_load(self.h, code, len(code), cm.xdim, cm.udim, cm.pdim)
+        if mid < _lib.MODEL_CUSTOM0:
+            raise RuntimeError(f"pmpc_model_load failed ({mid}) for {cm!r}")
+        self._custom[mid] = cm
+        return mid
+
+    def unload_model(self, model: int) -> None:
+        self._custom.pop(int(model), None)
+        if self.lib.pmpc_model_unload(self.h, int(model)) != 0:
+            raise ValueError(f"model {model} is not a custom model loaded on this solver")
+
+    def _check_custom(self, model, M, x=None, u=None, params=None):
+        """A loaded custom model reads x, u and pdim values per unit whatever the tensors hold: shapes that are not its own are
+        refused here (the library takes no dimensions with these calls).  Other ids pass: the library knows or refuses them."""
+        cm = self._custom.get(int(model))
+        if cm is None:
+            return
+        if (x is not None and x != cm.xdim) or (u is not None and u != cm.udim):
+            raise ValueError(f"{cm!r} (model {model}) was given states of {x} and controls of {u} entries")
+        if params is not None and tuple(params.shape) != (M, cm.pdim):
+            raise ValueError(f"{cm!r} (model {model}): params must be (M, pdim) = ({M}, {cm.pdim}), got {tuple(params.shape)}")
 
     def set_option(self, key: str, value: float) -> None:
         """Per-context algorithm switch (include/pmpc_abi.h, pmpc_set_option): e.g. ``set_option("xbox_as", 0)``."""
@@ -63,8 +97,9 @@ class DeviceSolver:
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.pmpc_destroy(self.h)
+            self.lib.pmpc_destroy(self.h)  # (unloads the custom models with everything else)
             self.h = None
+            self._custom = {}
 
     def __del__(self):
         try:
@@ -206,9 +241,10 @@ class DeviceSolver:
         return J
 
     def linearize(self, model: int, x0, X_prev, U_prev, params, f=None, fx=None, fu=None, wait_current_stream=True):
-        """f, fx, fu (ABI layout) at X_ = [x0, X_prev[:-1]], U_prev for a built-in model."""
+        """f, fx, fu (ABI layout) at X_ = [x0, X_prev[:-1]], U_prev for a built-in model or a loaded custom one (`load_model`)."""
         M, N, x = X_prev.shape
         u = U_prev.shape[-1]
+        self._check_custom(model, M, x, u, params)
         dev = X_prev.device
         f = torch.empty((M, N, x), dtype=torch.float64, device=dev) if f is None else f
         fx = torch.empty((M, N, x, x), dtype=torch.float64, device=dev) if fx is None else fx
@@ -232,6 +268,7 @@ class DeviceSolver:
         M, N, _ = U.shape
         x = x0.shape[-1]
         assert x0.shape == (M, x), (x0.shape, U.shape)
+        self._check_custom(model, M, x, U.shape[-1], params)
         out = torch.empty((M, N, x), dtype=torch.float64, device=U.device) if out is None else out
         assert out.shape == (M, N, x)
         self._before(wait_current_stream)
@@ -250,6 +287,7 @@ class DeviceSolver:
         M, N, x = X.shape
         u = U.shape[-1]
         assert U.shape == (M, N, u) and (U_tail is None or U_tail.shape == (M, int(s), u)), (X.shape, U.shape)
+        self._check_custom(model, M, x, u, params)
         X_out = torch.empty_like(X) if X_out is None else X_out
         U_out = torch.empty_like(U) if U_out is None else U_out
         um1_out = torch.empty((M, u), dtype=torch.float64, device=U.device) if um1_out is None else um1_out
@@ -498,7 +536,8 @@ class DeviceSolver:
 
     def scp_loop(self, model: int, params, steps: int, *, f2, fx2, fu2, first_cold=True, res=None, wait_current_stream=True, cost=None, cstr=None,
                  aug=None, **kw):
-        """`steps` SCP iterations (linearise -> sub-problem -> residual -> swap) for a built-in dynamics model in ONE library
+        """`steps` SCP iterations (linearise -> sub-problem -> residual -> swap) for a built-in dynamics model (or a custom one, by the
+        id of `load_model`: dense float64 Jacobians, refused with status 2 next to float32 matrices) in ONE library
         call: the host is out of the loop body (no Python / ctypes work between iterations, the residual and the next
         linearisation are enqueued behind the sub-problem's rounds before their outcome is read back).  `kw` as for
         `lqp_solve` / `lsoc_solve` with `f, fx, fu` (scratch the linearisation writes), `X_prev, U_prev` (start iterate,
@@ -519,6 +558,7 @@ class DeviceSolver:
         infos = (_lib.PmpcInfo * steps)()
         last = ctypes.c_int(0)
         M, N, x = kw["f"].shape
+        self._check_custom(model, M, params=params)  # (dimensions that are not the problem's: the library refuses them, status 2)
         if cost is not None:
             sc, keep = self._scp_cost(cost, N, x, f2.device)
         if cstr is not None:

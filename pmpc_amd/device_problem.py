@@ -15,6 +15,7 @@ from typing import Any, Dict, Optional
 import numpy as np
 import torch
 
+from .custom_model import CustomModel
 from .dynamics import model_id
 
 _CONE_SOLVERS = ("ecos", "gurobi", "mosek", "cosmo")  # static_backend.py:242-253
@@ -52,7 +53,7 @@ class DeviceProblem:
     slew0: Optional[torch.Tensor]  # slew_reg0 if there is a u0_slew to apply it to, else None (static_backend.py:263-272)
     um1: Optional[torch.Tensor]  # (M, u) u0_slew, None without slew_reg
     soc_kw: Dict[str, Any]  # the stage cone's keywords of `lsoc_solve` / `scp_loop`; {} if there is none
-    model: Optional[int]
+    model: Any  # the id of a built-in model, a CustomModel (the solver that runs it gives it an id: DeviceSolver.load_model), or None
     params: Optional[torch.Tensor]
 
     def solve_kw(self) -> Dict[str, Any]:
@@ -114,9 +115,12 @@ def build_problem(Q, R, x0=None, X_ref=None, U_ref=None, X_prev=None, U_prev=Non
     slew = full(slew_rate) if slew_rate is not None and float(slew_rate) != 0.0 else None
     slew_reg0 = full(settings["slew_reg"]) if "slew_reg" in settings else None
     um1 = T(u0_slew).reshape(-1, udim).expand(M, udim).contiguous() if slew_reg0 is not None and u0_slew is not None else None
-    model = model_id(builtin_model) if builtin_model is not None else None
+    custom = isinstance(builtin_model, CustomModel)
+    model = builtin_model if custom else (model_id(builtin_model) if builtin_model is not None else None)
     if model is not None:
-        assert params is not None, "builtin_model needs `params` (M, 3) unicycle / (M, 4) quadrotor / (M, 2) bicycle"
+        assert params is not None, "builtin_model needs `params` (M, 3) unicycle / (M, 4) quadrotor / (M, 2) bicycle / (M, pdim) CustomModel"
+        if custom:
+            model.check_problem(M, xdim, udim, params)
         params = own(T(params).reshape(M, -1).contiguous())
     return DeviceProblem(M=M, N=N, xdim=xdim, udim=udim, single=single, Q=Q, R=R, Qa=Qa, Ra=Ra, sym=sym,
                          x0=None if x0 is None else x0.contiguous(), X_ref=X_ref, U_ref=U_ref, X_prev=X_prev, U_prev=U_prev, lx=lx, ux=ux,

@@ -33,6 +33,10 @@ through the library loop: every sub-problem runs at `xdim + K` states on augment
 stays at `xdim`.  `set_keepout` writes new centres / radii into the resident arrays.  Refused next to it, before a device is touched: a
 stage cone (`soc=` / `extra_cstrs`), slew penalties, a sharded context, `xdim + K > 16`.
 
+`builtin_model=` also takes a `pmpc_amd.CustomModel`: the user's own x+ = F(x, u; p) as a short piece of device code, compiled at run
+time with automatic differentiation for its Jacobians and loaded on the controller's solver (`DeviceSolver.load_model`); `params` is
+then (M, pdim).  Cost, keep-out and `warm_shift` work as with a built-in name; the loop runs on dense Jacobians (no compact records).
+
 Refused with a ValueError (the library loop has no place for them): a Python `f_fx_fu_fn` / `lin_cost_fn` / `cost_fn`, `extra_cstrs_fns`,
 filters, `solver_state`, a sharded context, and `solver_settings` keys other than `solver`, `Nc`, `smooth_alpha`, `slew_reg`,
 `extra_cstrs`, `soc_u_interior`.  `soc=` / `solver_settings["extra_cstrs"]` (one stage-wise second-order cone) are taken as in
@@ -48,6 +52,7 @@ import torch
 
 from .device import DeviceSolver
 from .device_problem import build_problem, keepout_buffers
+from .custom_model import CustomModel
 from .dynamics import model_id
 
 _SETTINGS = ("solver", "Nc", "smooth_alpha", "slew_reg", "extra_cstrs", "soc_u_interior")
@@ -101,11 +106,14 @@ class MPCController:
             raise ValueError(f"MPCController: solver_settings {sorted(bad)} are not taken by the library's SCP loop (taken: {_SETTINGS})")
         if params is None or Q is None or R is None:
             raise ValueError("MPCController needs params=, Q= and R=")
-        self.model = model_id(builtin_model)
+        custom = isinstance(builtin_model, CustomModel)
+        self.model = None if custom else model_id(builtin_model)  # (a custom model: the id the solver loads it under, below)
         dev = torch.device(device)
         self.device = dev
         if np.ndim(Q) != 4 or np.ndim(R) != 4:
             raise ValueError("MPCController: Q (M, N, x, x) and R (M, N, u, u)")
+        if custom:  # dimensions and params that are not the model's: likewise before any device is touched
+            builtin_model.check_problem(np.shape(Q)[0], np.shape(Q)[-1], np.shape(R)[-1], params)
         if keepout is not None:  # a description the kernels cannot run: likewise before any device is touched
             from .extra_cstrs import _keepout_arrays
 
@@ -121,6 +129,8 @@ class MPCController:
         if solver.world > 1:
             raise ValueError("MPCController: a sharded context (comm_world > 1) is not supported")
         self.solver = s = solver
+        if custom:
+            self.model = s.load_model(builtin_model)
         # the problem as the library takes it (device_problem.py), with copies of the references, boxes and params of its own:
         # `set_reference` and `reset` write the references in place
         p = build_problem(Q, R, None, X_ref, U_ref, None, None, x_l, x_u, u_l, u_u, reg_x, reg_u, slew_rate, u0_slew, settings, soc, builtin_model,

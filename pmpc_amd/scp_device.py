@@ -6,7 +6,8 @@
 contract, README.md:136-145 / scp_mpc.py:338-342) and returns `f (M,N,x)`, `fx (M,N,x,x)`, `fu (M,N,x,u)` as torch GPU
 tensors in the usual (row, col) layout — or already in the ABI layout `(M,N,col,row)` with `jacobians_abi_layout=True`,
 which saves one transposing copy of the Jacobian stacks per iteration.  A built-in model (`builtin_model="unicycle" |
-"quadrotor" | "bicycle"`, `params=...`) is linearised by the HIP kernel of csrc/dynamics.hip instead of a Python callable.
+"quadrotor" | "bicycle"`, `params=...`) is linearised by the HIP kernel of csrc/dynamics.hip instead of a Python callable, and a
+`pmpc_amd.CustomModel` given there by the kernel compiled at run time from the user's device code (csrc/model_jit.hip).
 Nothing crosses PCIe inside the loop except the scalars of the `hist` row (one small read per SCP iteration); a built-in cost's
 descriptor is uploaded once before the loop, and the shifts' counter of refused blocks is read once after it.
 
@@ -40,6 +41,7 @@ from typing import Any, Callable, Dict, Optional
 
 import torch
 
+from .custom_model import CustomModel
 from .device import DeviceSolver
 from .device_problem import build_problem, keepout_buffers
 from .utils import TablePrinter
@@ -75,7 +77,7 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
                      x_u=None, u_l=None, u_u=None, verbose: bool = False, max_it: int = 100, time_limit: float = 1000.0,
                      res_tol: float = 1e-5, reg_x: float = 1e0, reg_u: float = 1e-2, slew_rate: Optional[float] = None,
                      u0_slew=None, solver_settings: Optional[Dict[str, Any]] = None, device="cuda",
-                     jacobians_abi_layout: bool = False, builtin_model: Optional[str] = None, params=None,
+                     jacobians_abi_layout: bool = False, builtin_model=None, params=None,
                      return_torch: bool = False, solver: Optional[DeviceSolver] = None, soc: Optional[Dict[str, Any]] = None,
                      lin_cost_fn=None, builtin_cost: Optional[Dict[str, Any]] = None, cost_fn=None,
                      extra_cstrs_fns=None, solver_state=None, filter_method: str = "", debug: bool = False,
@@ -96,6 +98,7 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
     X_prev, U_prev = p.X_prev, p.U_prev
     T = lambda z: torch.as_tensor(z, dtype=torch.float64, device=dev)  # (lin_cost_fn's gradients)
     s = solver or _solver_for(dev)
+    model = s.load_model(p.model) if isinstance(p.model, CustomModel) else p.model  # (a custom model: compiled and loaded once per solver)
     Xs = torch.empty((M, N, xdim), dtype=torch.float64, device=dev)
     Us = torch.empty((M, N, udim), dtype=torch.float64, device=dev)
     static_kw = dict(p.solve_kw(), slew_reg0=p.slew0, slew_um1=p.um1, X_out=Xs, U_out=Us, verbose=p.solver_verbose)
@@ -117,8 +120,8 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
     it, max_res = 0, math.inf
     s.stream.wait_stream(torch.cuda.current_stream(dev))  # the set-up above ran on the caller's stream
     while it < max_it:
-        if p.model is not None:
-            f, fxa, fua = s.linearize(p.model, p.x0, X_prev, U_prev, p.params)
+        if model is not None:
+            f, fxa, fua = s.linearize(model, p.x0, X_prev, U_prev, p.params)
         else:
             X_lin = torch.cat([p.x0[:, None, :], X_prev[:, :-1, :]], 1)
             f, fx, fu = f_fx_fu_fn(X_lin if not single else X_lin[0], U_prev if not single else U_prev[0])

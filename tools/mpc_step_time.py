@@ -6,6 +6,7 @@ solver (bench.py is); the numbers of CHANGELOG.md's MPCController entry come fro
     python tools/mpc_step_time.py --model quadrotor --M 4096 --N 50 --steps 50 --iterations 3
     python tools/mpc_step_time.py --model bicycle --keepout 2        # both versions with a keep-out constraint of 2 balls per particle
     python tools/mpc_step_time.py --model bicycle --iterations 1 --warm-shift --no-solve   # MPCController(warm_shift=True): the same episode
+    python tools/mpc_step_time.py --custom-model --no-solve      # the bicycle written as a pmpc_amd.CustomModel (compiled at run time)
 
 Kernel times: HIP events on the solver's stream around single launches, all shapes warmed first, the kernels alternating in one loop.
 Step times: host clock around calls that end with a device->host read (both are synchronous), the two versions alternating step by step
@@ -26,16 +27,19 @@ def _stats(v):
     return dict(median=float(np.median(v)), min=float(v.min()), max=float(v.max()), p10=float(np.percentile(v, 10)), p90=float(np.percentile(v, 90)))
 
 
-def kernel_times(solver, mid, d, reps=30):
-    """Median / spread in microseconds of one launch of rollout, shift_plan (s = 1), linearize and shift_active_set (s = 1)."""
+def kernel_times(solver, mid, d, reps=30, also=None):
+    """Median / spread in microseconds of one launch of rollout, shift_plan (s = 1), linearize and shift_active_set (s = 1).
+    `also`: a second model id of the same dimensions, whose three kernels take turns with the first one's ("<kernel>_also")."""
     import torch
 
     X, U = d["X_prev"], d["U_prev"]
     Xo, Uo, um1 = torch.empty_like(X), torch.empty_like(U), torch.empty((U.shape[0], U.shape[2]), dtype=torch.float64, device=U.device)
     f, fx, fu = solver.linearize(mid, d["x0"], X, U, d["params"])
-    jobs = {"rollout": lambda: solver.rollout(mid, d["x0"], U, d["params"], out=Xo, wait_current_stream=False)}
-    jobs["shift_plan"] = lambda: solver.shift_plan(mid, X, U, d["params"], s=1, X_out=Xo, U_out=Uo, um1_out=um1, wait_current_stream=False)
-    jobs["linearize"] = lambda: solver.linearize(mid, d["x0"], X, U, d["params"], f, fx, fu, wait_current_stream=False)
+    jobs = {}
+    for m, tag in [(mid, "")] + ([(also, "_also")] if also is not None else []):
+        jobs["rollout" + tag] = lambda m=m: solver.rollout(m, d["x0"], U, d["params"], out=Xo, wait_current_stream=False)
+        jobs["shift_plan" + tag] = lambda m=m: solver.shift_plan(m, X, U, d["params"], s=1, X_out=Xo, U_out=Uo, um1_out=um1, wait_current_stream=False)
+        jobs["linearize" + tag] = lambda m=m: solver.linearize(m, d["x0"], X, U, d["params"], f, fx, fu, wait_current_stream=False)
     if hasattr(solver.lib, "pmpc_shift_active_set_device") and d.get("lu") is not None:  # (an older library under A/B has none)
         act, act_o = torch.zeros(U.shape, dtype=torch.int32, device=U.device), torch.empty(U.shape, dtype=torch.int32, device=U.device)
         jobs["shift_active_set"] = lambda: solver.shift_active_set(act, U, d["lu"], d["uu"], 1, s=1, U_out=Uo, act_out=act_o, wait_current_stream=False)
@@ -53,6 +57,12 @@ def kernel_times(solver, mid, d, reps=30):
     return {k: _stats(v) for k, v in out.items()}
 
 
+def solver_arch(solver):
+    import torch
+
+    return torch.cuda.get_device_properties(solver.device).gcnArchName.split(":")[0]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--model", default="bicycle", choices=["unicycle", "quadrotor", "bicycle"])
@@ -65,6 +75,8 @@ def main():
                     "MPCController(keepout=...) against solve(builtin_cstr=...)")
     ap.add_argument("--warm-shift", action="store_true", help="MPCController(warm_shift=True): the active set is moved along with the plan and the first "
                     "iteration of a shifted step starts warm; the same episode otherwise")
+    ap.add_argument("--custom-model", action="store_true", help="the bicycle written as a pmpc_amd.CustomModel (tests/support/custom_models.py): compiled at "
+                    "run time, linearised by automatic differentiation; kernel times next to the built-in bicycle's (\"_also\")")
     ap.add_argument("--no-solve", action="store_true", help="leave the pmpc_amd.solve version out (kernel times and the controller only)")
     args = ap.parse_args()
 
@@ -77,7 +89,19 @@ def main():
     F = getattr(dyn, args.model)
     solver = DeviceSolver(0)
     result = dict(model=args.model, M=args.M, N=args.N, iterations=args.iterations, steps=args.steps)
-    result["kernel_us"] = kernel_times(solver, mid, to_device_problem(prob))
+    if args.custom_model:
+        if args.model != "bicycle":
+            raise SystemExit("--custom-model is the bicycle: --model bicycle")
+        from tests.support import custom_models
+
+        model = custom_models.make("bicycle")
+        t0 = time.perf_counter()
+        model.compile(arch=solver_arch(solver))
+        result["custom_model"], result["compile_ms"] = True, 1e3 * (time.perf_counter() - t0)
+        result["kernel_us"] = kernel_times(solver, solver.load_model(model), to_device_problem(prob), also=mid)  # ("_also": the built-in id)
+    else:
+        model = args.model
+        result["kernel_us"] = kernel_times(solver, mid, to_device_problem(prob))
 
     common = dict(X_ref=prob["X_ref"], U_ref=prob["U_ref"], u_l=prob["u_l"], u_u=prob["u_u"], reg_x=prob["reg_x"], reg_u=prob["reg_u"],
                   solver_settings=dict(solver="osqp", Nc=1))
@@ -91,7 +115,7 @@ def main():
     if args.warm_shift:
         ctl_kw["warm_shift"] = True
     result["warm_shift"] = bool(args.warm_shift)
-    ctl = pmpc_amd.MPCController(builtin_model=args.model, params=prob["params"], Q=prob["Q"], R=prob["R"], solver=solver, **ctl_kw, **common)
+    ctl = pmpc_amd.MPCController(builtin_model=model, params=prob["params"], Q=prob["Q"], R=prob["R"], solver=solver, **ctl_kw, **common)
     ctl.reset(X_prev=prob["X_prev"], U_prev=prob["U_prev"])
     Xs, Us = prob["X_prev"], prob["U_prev"]  # the solve version's warm start
     rng = np.random.default_rng(0)
@@ -107,7 +131,7 @@ def main():
             t2 = time.perf_counter()
             if not fresh:
                 Xs, Us, _ = dyn.shift_plan(mid, Xs, Us, prob["params"], s=1)
-            X, U, data = pmpc_amd.solve(None, prob["Q"], prob["R"], np.tile(x0, (args.M, 1)), device="cuda", builtin_model=args.model, params=prob["params"],
+            X, U, data = pmpc_amd.solve(None, prob["Q"], prob["R"], np.tile(x0, (args.M, 1)), device="cuda", builtin_model=model, params=prob["params"],
                                         X_prev=Xs, U_prev=Us, max_it=args.iterations, res_tol=0.0, verbose=False, **solve_kw, **common)  # (on the package's own context)
             t3 = time.perf_counter()
         if u0 is None or X is None:
