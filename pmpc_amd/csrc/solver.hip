@@ -1,6 +1,7 @@
-// solver.hip — host side of the device solver and the C ABI of include/pmpc_abi.h: contexts, options, communicators, profiling,
-// the structured Newton solve, the entry points of the QP path (fp32-storage protocol, slew increment form) and the SCP loop.
-// The solve itself — the phases below — is solver_qp.hip (QpSolve, one object per solve).
+// solver.hip — host side of the device solver and the C ABI of include/pmpc_abi.h: contexts, options, profiling, the structured
+// Newton solve, the thin device entries (one launch each) and the entry points of the QP path (fp32-storage protocol, slew increment
+// form).  The solve itself — the phases below — is solver_qp.hip (QpSolve, one object per solve); the SCP loop around it is
+// solver_scp.hip (ScpLoop), the communicators are comm.hip.
 //
 // One call = one convex sub-problem of the reference's SCP loop, i.e. what
 // PMPC.jl/src/main.jl:115-171 `lqp_solve` does (assemble joint QP -> OSQP -> split), solved here as
@@ -9,105 +10,9 @@
 //      system being the same structured solve with modified diagonals.
 // The only cross-particle (and therefore cross-GPU) data are the condensed consensus Hessian /
 // gradient [Hc | gc] and a handful of IPM scalars -> RCCL all-reduce when a communicator is set.
-#include <dlfcn.h>
-
 #include "solver_internal.h"
 #include "cost_lin.h"
-#include "keepout.h"
 #include "model_jit.h"
-#include <atomic>
-
-namespace {
-
-// ---- lazily bound RCCL (the library must load on machines where no communicator is ever made) ----
-struct Rccl {
-  void *h = nullptr;
-  ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-  ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*Broadcast)(const void *, void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-  bool load() {
-    if (h) return true;
-    const char *names[] = {"librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so"};  // torch bundles soname librccl.so: reuse the loaded copy
-    for (const char *n : names)
-      if ((h = dlopen(n, RTLD_NOW | RTLD_GLOBAL))) break;
-    if (!h) return false;
-    GetUniqueId = (decltype(GetUniqueId))dlsym(h, "ncclGetUniqueId");
-    CommInitRank = (decltype(CommInitRank))dlsym(h, "ncclCommInitRank");
-    CommDestroy = (decltype(CommDestroy))dlsym(h, "ncclCommDestroy");
-    AllReduce = (decltype(AllReduce))dlsym(h, "ncclAllReduce");
-    Broadcast = (decltype(Broadcast))dlsym(h, "ncclBroadcast");
-    return GetUniqueId && CommInitRank && AllReduce && Broadcast;
-  }
-};
-Rccl g_rccl;
-
-// ---- in-process communicator (TEST HOOK, pmpc_comm_init_mock) --------------------------------------------------------
-// RCCL refuses two ranks on one device, so on a single-GPU box the world > 1 code paths (packed scalar exchange, consensus
-// all-reduce, owner / bounds broadcast) could never run.  This stand-in lets N contexts on ONE device, each driven by its
-// own host thread, play the ranks: a collective synchronises the caller's stream, meets the other ranks at a barrier,
-// reduces on the host in rank order and writes the result back.  Same call signature as the RCCL entry points it
-// replaces; correctness only, no performance meaning.
-struct MockGroup {
-  int world = 0, arrived = 0, generation = 0;
-  std::mutex m;
-  std::condition_variable cv;
-  std::vector<std::vector<unsigned char>> slot;  // one staging buffer per rank
-  void barrier() {
-    std::unique_lock<std::mutex> lk(m);
-    const int gen = generation;
-    if (++arrived == world) { arrived = 0; generation++; cv.notify_all(); }
-    else cv.wait(lk, [&] { return gen != generation; });
-  }
-};
-struct MockRank { MockGroup *g; int rank; };
-std::map<int, MockGroup *> g_mock_groups;
-std::mutex g_mock_mutex;
-
-template <class T>
-void mock_reduce(MockGroup *g, size_t n, ncclRedOp_t op, T *out) {
-  for (size_t k = 0; k < n; k++) {
-    T acc = ((const T *)g->slot[0].data())[k];
-    for (int r = 1; r < g->world; r++) {
-      const T v = ((const T *)g->slot[r].data())[k];
-      acc = op == ncclSum ? (T)(acc + v) : (op == ncclMin ? std::min(acc, v) : std::max(acc, v));
-    }
-    out[k] = acc;
-  }
-}
-ncclResult_t mock_allreduce(const void *send, void *recv, size_t n, ncclDataType_t dt, ncclRedOp_t op, ncclComm_t comm, hipStream_t s) {
-  MockRank *mr = (MockRank *)comm;
-  MockGroup *g = mr->g;
-  const size_t esz = dt == ncclFloat64 ? 8 : 4;
-  HIP_CHECK(hipStreamSynchronize(s));
-  g->slot[mr->rank].resize(n * esz);
-  HIP_CHECK(hipMemcpy(g->slot[mr->rank].data(), send, n * esz, hipMemcpyDeviceToHost));
-  g->barrier();
-  std::vector<unsigned char> out(n * esz);
-  if (dt == ncclFloat64) mock_reduce<double>(g, n, op, (double *)out.data());
-  else mock_reduce<int>(g, n, op, (int *)out.data());
-  g->barrier();  // everyone has read the slots before anyone overwrites them in the next collective
-  HIP_CHECK(hipMemcpy(recv, out.data(), n * esz, hipMemcpyHostToDevice));
-  return ncclSuccess;
-}
-ncclResult_t mock_broadcast(const void *send, void *recv, size_t n, ncclDataType_t dt, int root, ncclComm_t comm, hipStream_t s) {
-  MockRank *mr = (MockRank *)comm;
-  MockGroup *g = mr->g;
-  const size_t esz = dt == ncclFloat64 ? 8 : 4;
-  HIP_CHECK(hipStreamSynchronize(s));
-  if (mr->rank == root) {
-    g->slot[root].resize(n * esz);
-    HIP_CHECK(hipMemcpy(g->slot[root].data(), send, n * esz, hipMemcpyDeviceToHost));
-  }
-  g->barrier();
-  std::vector<unsigned char> out(g->slot[root].begin(), g->slot[root].begin() + n * esz);
-  g->barrier();
-  HIP_CHECK(hipMemcpy(recv, out.data(), n * esz, hipMemcpyHostToDevice));
-  return ncclSuccess;
-}
-
-}  // namespace
 
 static const struct { const char *key, *env; double dflt; } kPmpcOptions[OPT_COUNT] = {
     {"as_warm", "PMPC_AS_WARM", 1},                // warm start of the active-set rounds from the previous solve's set
@@ -135,23 +40,6 @@ static const struct { const char *key, *env; double dflt; } kPmpcOptions[OPT_COU
 };
 
 namespace pmpc_impl {
-
-
-void allreduce(pmpc_ctx *c, void *buf, size_t n, ncclDataType_t dt, ncclRedOp_t op) {
-  if (!c->multi()) return;
-  ncclResult_t r = g_rccl.AllReduce(buf, buf, n, dt, op, c->comm, c->stream);
-  if (r != ncclSuccess) {
-    fprintf(stderr, "pmpc_hip: ncclAllReduce failed (%d)\n", (int)r);
-    throw PmpcHipError{(int)r, "ncclAllReduce", __FILE__, __LINE__};
-  }
-}
-void broadcast(pmpc_ctx *c, void *buf, size_t n, ncclDataType_t dt, int root) {
-  ncclResult_t r = g_rccl.Broadcast(buf, buf, n, dt, root, c->comm, c->stream);
-  if (r != ncclSuccess) {
-    fprintf(stderr, "pmpc_hip: ncclBroadcast failed (%d)\n", (int)r);
-    throw PmpcHipError{(int)r, "ncclBroadcast", __FILE__, __LINE__};
-  }
-}
 
 // wait until the device has published sequence number `want` into host-coherent memory; stream sync after 2 s of polling
 void wait_published(pmpc_ctx *c, volatile unsigned long long *seq, unsigned long long want) {
@@ -303,6 +191,28 @@ void fill_nan_outputs(pmpc_ctx *c, const pmpc_problem *p) {
   HIP_CHECK(hipStreamSynchronize(c->stream));
 }
 
+// The counter of blocks the reference shift refused (cost_lin.hip) lives in the workspace, zeroed when it is created.
+unsigned *cost_bad_counter(pmpc_ctx *c) {
+  if (c->ws.cost_bad.ensure(sizeof(unsigned))) HIP_CHECK(hipMemsetAsync(c->ws.cost_bad.p, 0, sizeof(unsigned), c->stream));
+  return (unsigned *)c->ws.cost_bad.p;
+}
+
+// A thin device entry, after its own argument checks: the context's device, `body` (the launch) and the check for a refused launch
+// timed in `prof_class` if the entry has one; a failed HIP call is the entry's own `hip_error_status`.
+template <class F>
+static int device_entry(pmpc_ctx *c, int hip_error_status, F body, int prof_class = -1) {
+  try {
+    HIP_CHECK(hipSetDevice(c->device));
+    std::optional<ProfScope> ps;
+    if (prof_class >= 0) ps.emplace(c, prof_class);
+    body();
+    HIP_CHECK(hipGetLastError());
+  } catch (const PmpcHipError &) {
+    return hip_error_status;
+  }
+  return 0;
+}
+
 }  // namespace pmpc_impl
 
 // =================================================================================================
@@ -369,8 +279,7 @@ void pmpc_destroy(pmpc_ctx *c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   custom_models_unload_all(c);  // runtime-compiled models loaded on this context (model_jit.hip)
-  if (c->comm && c->mock_comm) delete (MockRank *)c->comm;
-  else if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
+  comm_release(c);
   Workspace &w = c->ws;
   DevBuf *all[] = {&w.X, &w.U, &w.dX, &w.dU, &w.dX2, &w.dU2, &w.xm, &w.xd, &w.um, &w.ud, &w.K, &w.Hinv, &w.kff, &w.gc_part, &w.Hc_part, &w.Hc_w, &w.gc_w, &w.cons_w, &w.epi_lam, &w.epi_out, &w.epi_gath, &w.es_Dx, &w.es_wx, &w.es_Du, &w.es_wu, &w.es_xm, &w.es_xd, &w.es_um, &w.es_ud, &w.es_kff2, &w.es_kff3, &w.es_gc2, &w.es_dots, &w.es_coef, &w.es_out2, &w.es_Xt, &w.es_Ut, &w.es_U, &w.es_zero, &w.scratch,
                    &w.red_tmp, &w.Hg, &w.Lc, &w.duc, &w.xch, &w.zeros, &w.zslew, &w.zslew0, &w.zum1, &w.part_sum, &w.part_cnt,
@@ -441,121 +350,35 @@ void pmpc_restart_stats(pmpc_ctx *c, unsigned long long *out4, int reset) {
   if (reset) HIP_WARN(hipMemset(c->ws.ck_stat.p, 0, 4 * sizeof(unsigned long long)));
 }
 
-int pmpc_comm_unique_id(void *out128) {
-  if (!g_rccl.load()) return 1;
-  ncclUniqueId id;
-  if (g_rccl.GetUniqueId(&id) != ncclSuccess) return 2;
-  memcpy(out128, &id, sizeof(id));
-  return 0;
-}
-
-int pmpc_comm_init(pmpc_ctx *c, int rank, int world, const void *id128) {
-  // TEST HOOK: PMPC_RCCL_SINGLE=1 makes a world of one a real 1-rank RCCL communicator and sends every solve through the
-  // multi-rank code paths (packed exchange, consensus all-reduce, bounds broadcast) — the only way to run the actual
-  // ncclAllReduce / ncclBroadcast calls on a one-GPU box (RCCL refuses two ranks on one device).
-  const char *single = getenv("PMPC_RCCL_SINGLE");
-  if (world <= 1 && !(single && single[0] == '1')) {
-    c->rank = 0;
-    c->world = 1;
-    return 0;
-  }
-  if (world <= 1) { world = 1; rank = 0; c->single_rank_comm = true; }
-  if (!g_rccl.load()) return 1;
-  if (hipSetDevice(c->device) != hipSuccess) return 3;
-  ncclUniqueId id;
-  memcpy(&id, id128, sizeof(id));
-  if (g_rccl.CommInitRank(&c->comm, world, id, rank) != ncclSuccess) return 2;
-  c->rank = rank;
-  c->world = world;
-  return 0;
-}
-// TEST HOOK: join the in-process communicator `group` (see MockGroup above) as rank `rank` of `world`.  Every context of
-// the group lives on one device and must be driven by its own host thread.  Installs the stand-in collectives
-// process-wide: do not mix with a real RCCL communicator in the same process.
-int pmpc_comm_init_mock(pmpc_ctx *c, int rank, int world, int group) {
-  std::lock_guard<std::mutex> lk(g_mock_mutex);
-  MockGroup *&g = g_mock_groups[group];
-  if (!g) {
-    g = new MockGroup();
-    g->world = world;
-    g->slot.resize(world);
-  }
-  if (g->world != world || rank < 0 || rank >= world) return 1;
-  g_rccl.AllReduce = mock_allreduce;
-  g_rccl.Broadcast = mock_broadcast;
-  c->comm = (ncclComm_t) new MockRank{g, rank};
-  c->mock_comm = true;
-  c->rank = rank;
-  c->world = world;
-  return 0;
-}
 int pmpc_comm_rank(pmpc_ctx *c) { return c->rank; }
 int pmpc_comm_world(pmpc_ctx *c) { return c->world; }
 
 int pmpc_scp_residual_device(pmpc_ctx *c, size_t xdim, size_t udim, size_t N, size_t M, const double *X, const double *X_prev,
                              const double *U, const double *U_prev, double *out) {
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
-    ProfScope ps(c, 7);
-    launch_scp_residual(X, X_prev, U, U_prev, (long long)M * (long long)N, (int)xdim, (int)udim, out, c->stream);
-    HIP_CHECK(hipGetLastError());
-  } catch (const PmpcHipError &) {
-    return 2;
-  }
-  return 0;
+  return device_entry(c, 2, [&] { launch_scp_residual(X, X_prev, U, U_prev, (long long)M * (long long)N, (int)xdim, (int)udim, out, c->stream); }, 7);
 }
 
 int pmpc_linearize_device_f32(pmpc_ctx *c, int model, size_t N, size_t M, const double *x0, const double *X_prev,
                               const double *U_prev, const double *params, double *f, float *fx, float *fu) {
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
-    if (!model_known(model)) return 2;  // (built-in ids only: a runtime-compiled model writes fp64 Jacobians)
-    ProfScope ps(c, 6);
-    launch_linearize(model, (int)N, (int)M, x0, X_prev, U_prev, params, f, (double *)fx, (double *)fu, c->stream, 1);
-    HIP_CHECK(hipGetLastError());
-  } catch (const PmpcHipError &) {
-    return 2;
-  }
-  return 0;
+  if (!model_known(model)) return 2;  // (built-in ids only: a runtime-compiled model writes fp64 Jacobians)
+  return device_entry(c, 2, [&] { launch_linearize(model, (int)N, (int)M, x0, X_prev, U_prev, params, f, (double *)fx, (double *)fu, c->stream, 1); }, 6);
 }
 
 int pmpc_linearize_device(pmpc_ctx *c, int model, size_t N, size_t M, const double *x0, const double *X_prev,
                           const double *U_prev, const double *params, double *f, double *fx, double *fu) {
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
-    if (!model_known(c, model)) return 2;
-    ProfScope ps(c, 6);
-    launch_linearize(model, (int)N, (int)M, x0, X_prev, U_prev, params, f, fx, fu, c->stream);
-    HIP_CHECK(hipGetLastError());
-  } catch (const PmpcHipError &) {
-    return 2;
-  }
-  return 0;
+  if (!model_known(c, model)) return 2;
+  return device_entry(c, 2, [&] { launch_linearize(model, (int)N, (int)M, x0, X_prev, U_prev, params, f, fx, fu, c->stream); }, 6);
 }
 
 // Nonlinear rollout and receding-horizon shift of a built-in or runtime-compiled model (dynamics.hip, model_jit.hip): asynchronous on the context's stream.
 int pmpc_rollout_device(pmpc_ctx *c, int model, size_t N, size_t M, const double *x0, const double *U, const double *params, double *X) {
   if (!c || !model_known(c, model) || N == 0 || M == 0 || !x0 || !U || !params || !X) return 2;
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
-    launch_rollout(model, (int)N, (int)M, x0, U, params, X, c->stream);
-    HIP_CHECK(hipGetLastError());
-  } catch (const PmpcHipError &) {
-    return 1;
-  }
-  return 0;
+  return device_entry(c, 1, [&] { launch_rollout(model, (int)N, (int)M, x0, U, params, X, c->stream); });
 }
 int pmpc_shift_plan_device(pmpc_ctx *c, int model, size_t N, size_t M, size_t s, const double *X, const double *U, const double *params,
                            const double *U_tail, double *X_new, double *U_new, double *um1_new) {
   if (!c || !model_known(c, model) || N == 0 || M == 0 || s < 1 || s >= N || !X || !U || !params || !X_new || !U_new || X_new == X || U_new == U) return 2;
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
-    launch_shift_plan(model, (int)N, (int)M, (int)s, X, U, params, U_tail, X_new, U_new, um1_new, c->stream);
-    HIP_CHECK(hipGetLastError());
-  } catch (const PmpcHipError &) {
-    return 1;
-  }
-  return 0;
+  return device_entry(c, 1, [&] { launch_shift_plan(model, (int)N, (int)M, (int)s, X, U, params, U_tail, X_new, U_new, um1_new, c->stream); });
 }
 
 // The control-box statuses of a plan moved along with its controls (dynamics.hip, k_shift_active_set): on the caller's arrays, and on
@@ -567,14 +390,8 @@ static bool shift_set_args_ok(const pmpc_ctx *c, size_t N, size_t M, size_t udim
 int pmpc_shift_active_set_device(pmpc_ctx *c, size_t N, size_t M, size_t udim, long long Nc, size_t s, const double *U, const double *U_tail, const int *act,
                                  const double *lo, const double *hi, double *U_new, int *act_new) {
   if (!shift_set_args_ok(c, N, M, udim, s, U, U_new) || !act || !act_new || act_new == act) return 2;
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
-    launch_shift_active_set((int)N, (int)M, (int)udim, Nc < 0 || Nc > (long long)N ? (int)N : (int)Nc, (int)s, U, U_tail, act, lo, hi, U_new, act_new, c->stream);
-    HIP_CHECK(hipGetLastError());
-  } catch (const PmpcHipError &) {
-    return 1;
-  }
-  return 0;
+  const int nc = Nc < 0 || Nc > (long long)N ? (int)N : (int)Nc;
+  return device_entry(c, 1, [&] { launch_shift_active_set((int)N, (int)M, (int)udim, nc, (int)s, U, U_tail, act, lo, hi, U_new, act_new, c->stream); });
 }
 int pmpc_warm_shift_device(pmpc_ctx *c, size_t N, size_t M, size_t udim, long long Nc, size_t s, const double *U, const double *U_tail, const double *lo,
                            const double *hi, double *U_new, int *shifted) {
@@ -584,46 +401,25 @@ int pmpc_warm_shift_device(pmpc_ctx *c, size_t N, size_t M, size_t udim, long lo
   const size_t n = M * N * udim, bytes = n * sizeof(int) + 8;  // (+ 8: the sweeps read the last status as 8 bytes)
   // (a sharded context's shared controls follow global particle 0, which this rank may not hold: its first solve stays cold)
   if (w.as_key == -1 || w.as_count != n || w.as_act.bytes < bytes || c->multi()) return 0;
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
+  const int st = device_entry(c, 1, [&] {
     if (w.as_act2.ensure(w.as_act.bytes)) HIP_CHECK(hipMemsetAsync(w.as_act2.p, 0, w.as_act2.bytes, c->stream));
     launch_shift_active_set((int)N, (int)M, (int)udim, Nc < 0 || Nc > (long long)N ? (int)N : (int)Nc, (int)s, U, U_tail, (const int *)w.as_act.p, lo, hi, U_new,
                             (int *)w.as_act2.p, c->stream);
-    HIP_CHECK(hipGetLastError());
-    std::swap(w.as_act, w.as_act2);  // (same size: the solve's own ensure() finds its buffer as large as before)
-    *shifted = 1;
-  } catch (const PmpcHipError &) {
-    return 1;
-  }
+  });
+  if (st != 0) return st;
+  std::swap(w.as_act, w.as_act2);  // (same size: the solve's own ensure() finds its buffer as large as before)
+  *shifted = 1;
   return 0;
 }
 int pmpc_warm_set_read_device(pmpc_ctx *c, int *act_out, size_t n) {
   if (!c || !act_out || c->ws.as_key == -1 || c->ws.as_count != n || c->ws.as_act.bytes < n * sizeof(int)) return 2;
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipMemcpyAsync(act_out, c->ws.as_act.p, n * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-  } catch (const PmpcHipError &) {
-    return 1;
-  }
-  return 0;
+  return device_entry(c, 1, [&] { HIP_CHECK(hipMemcpyAsync(act_out, c->ws.as_act.p, n * sizeof(int), hipMemcpyDeviceToDevice, c->stream)); });
 }
 
-// Linearised nonlinear costs (cost_lin.hip).  The counter of refused blocks lives in the workspace, zeroed when it is created.
-static unsigned *cost_bad_counter(pmpc_ctx *c) {
-  if (c->ws.cost_bad.ensure(sizeof(unsigned))) HIP_CHECK(hipMemsetAsync(c->ws.cost_bad.p, 0, sizeof(unsigned), c->stream));
-  return (unsigned *)c->ws.cost_bad.p;
-}
+// Linearised nonlinear costs (cost_lin.hip).
 int pmpc_ref_shift_device(pmpc_ctx *c, size_t dim, size_t rows, const double *A, const double *cv, const double *ref, double *out) {
   if (dim < 1 || dim > (size_t)REF_SHIFT_MAX_DIM) return 2;
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
-    ProfScope ps(c, 6);
-    launch_ref_shift((int)dim, (long long)rows, A, cv, ref, out, cost_bad_counter(c), c->stream);
-    HIP_CHECK(hipGetLastError());
-  } catch (const PmpcHipError &) {
-    return 1;
-  }
-  return 0;
+  return device_entry(c, 1, [&] { launch_ref_shift((int)dim, (long long)rows, A, cv, ref, out, cost_bad_counter(c), c->stream); }, 6);
 }
 long long pmpc_ref_shift_bad_pivots(pmpc_ctx *c, int reset) {
   if (!c || !c->ws.cost_bad.p) return 0;
@@ -636,28 +432,12 @@ long long pmpc_ref_shift_bad_pivots(pmpc_ctx *c, int reset) {
 }
 int pmpc_obstacle_cost_grad_device(pmpc_ctx *c, const pmpc_scp_cost *cost, size_t xdim, size_t N, size_t M, const double *X_prev, double *cx) {
   if (!obstacle_cost_valid(cost, (int)xdim)) return 2;
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
-    ProfScope ps(c, 6);
-    launch_obstacle_grad(*cost, (int)xdim, (int)N, (int)M, X_prev, cx, c->stream);
-    HIP_CHECK(hipGetLastError());
-  } catch (const PmpcHipError &) {
-    return 1;
-  }
-  return 0;
+  return device_entry(c, 1, [&] { launch_obstacle_grad(*cost, (int)xdim, (int)N, (int)M, X_prev, cx, c->stream); }, 6);
 }
 int pmpc_obstacle_ref_shift_device(pmpc_ctx *c, const pmpc_scp_cost *cost, size_t xdim, size_t N, size_t M, const double *X_prev, const double *Q,
                                    const double *X_ref, double *out) {
   if (!obstacle_cost_valid(cost, (int)xdim)) return 2;
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
-    ProfScope ps(c, 6);
-    launch_obstacle_ref_shift(*cost, (int)xdim, (int)N, (int)M, X_prev, Q, X_ref, out, cost_bad_counter(c), c->stream);
-    HIP_CHECK(hipGetLastError());
-  } catch (const PmpcHipError &) {
-    return 1;
-  }
-  return 0;
+  return device_entry(c, 1, [&] { launch_obstacle_ref_shift(*cost, (int)xdim, (int)N, (int)M, X_prev, Q, X_ref, out, cost_bad_counter(c), c->stream); }, 6);
 }
 
 // compact Jacobian records of a built-in model (jac_compact.h), as the SCP loop writes and reads them: the linearisation into jc
@@ -665,27 +445,12 @@ int pmpc_obstacle_ref_shift_device(pmpc_ctx *c, const pmpc_scp_cost *cost, size_
 // (1) part of the records.  pmpc_jac_live_mask: the entries the records treat as live (host only; returns 100 xdim + udim).
 int pmpc_linearize_compact_device(pmpc_ctx *c, int model, size_t N, size_t M, const double *x0, const double *X_prev, const double *U_prev,
                                   const double *params, double *f, double *jc) {
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
-    if (!model_known(model)) return 2;
-    ProfScope ps(c, 6);
-    launch_linearize_compact(model, (int)N, (int)M, x0, X_prev, U_prev, params, f, jc, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream);
-    HIP_CHECK(hipGetLastError());
-  } catch (const PmpcHipError &) {
-    return 2;
-  }
-  return 0;
+  if (!model_known(model)) return 2;
+  return device_entry(c, 2, [&] { launch_linearize_compact(model, (int)N, (int)M, x0, X_prev, U_prev, params, f, jc, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream); }, 6);
 }
 int pmpc_expand_jac_device(pmpc_ctx *c, int model, size_t N, size_t M, const double *jc, double *fx, double *fu, int orient) {
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
-    if (!model_known(model)) return 2;
-    launch_expand_jac(model, (int)N, (int)M, jc, fx, fu, orient, c->stream);
-    HIP_CHECK(hipGetLastError());
-  } catch (const PmpcHipError &) {
-    return 2;
-  }
-  return 0;
+  if (!model_known(model)) return 2;
+  return device_entry(c, 2, [&] { launch_expand_jac(model, (int)N, (int)M, jc, fx, fu, orient, c->stream); });
 }
 long long pmpc_jac_compact_doubles(int model, size_t N, size_t M) { return model_known(model) ? jac_compact_doubles(model, (int)N, (int)M) : -1; }
 int pmpc_jac_live_mask(int model, unsigned char *fx_mask, unsigned char *fu_mask) { return jac_live_mask(model, fx_mask, fu_mask); }
@@ -837,220 +602,4 @@ int solve_slew_increment_form(pmpc_ctx *c, const pmpc_problem *p, pmpc_info *inf
   return st;
 }
 
-
-// -------------------------------------------------------------------------------------------------
-// SCP loop with the host out of the loop body (built-in dynamics)
-// -------------------------------------------------------------------------------------------------
-static std::atomic<unsigned long long> g_follow_ups[2];  // iterations whose follow-up was taken as enqueued behind the rounds / enqueued after the solve
-void pmpc_scp_loop_follow_ups(unsigned long long *out2, int reset) {
-  for (int k = 0; k < 2; k++) {
-    if (out2) out2[k] = g_follow_ups[k].load();
-    if (reset) g_follow_ups[k].store(0);
-  }
-}
-size_t pmpc_abi_scp_aug_size(void) { return sizeof(pmpc_scp_aug); }
-
-int pmpc_scp_loop_device(pmpc_ctx *c, int model, const double *params, const pmpc_problem *p0, double *f2, double *fx2, double *fu2,
-                         int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out) {
-  return pmpc_scp_loop_device_cstr(c, model, params, p0, f2, fx2, fu2, steps, first_cold, res, infos, last_in_out, nullptr, nullptr, nullptr);
-}
-int pmpc_scp_loop_device_cost(pmpc_ctx *c, int model, const double *params, const pmpc_problem *p0, double *f2, double *fx2, double *fu2,
-                              int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out, const pmpc_scp_cost *cost) {
-  return pmpc_scp_loop_device_cstr(c, model, params, p0, f2, fx2, fu2, steps, first_cold, res, infos, last_in_out, cost, nullptr, nullptr);
-}
-// every pointer of the augmented buffers is there
-static bool scp_aug_complete(const pmpc_scp_aug *g) {
-  if (!g || !g->Q || !g->x0 || !g->lx || !g->X_out) return false;
-  for (int k = 0; k < 2; k++)
-    if (!g->f[k] || !g->fx[k] || !g->fu[k] || !g->X_prev[k] || !g->X_ref[k] || !g->xu[k]) return false;
-  return true;
-}
-int pmpc_scp_loop_device_cstr(pmpc_ctx *c, int model, const double *params, const pmpc_problem *p0, double *f2, double *fx2, double *fu2,
-                              int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out, const pmpc_scp_cost *cost,
-                              const pmpc_scp_cstr *cstr, const pmpc_scp_aug *aug) {
-  pmpc_problem p = *p0;
-  const int x = (int)p0->xdim, u = (int)p0->udim, N = (int)p0->N, M = (int)p0->M;
-  // Built-in cost: the sub-problem of an iteration tracks X_ref - Q^-1 cx(X_prev).  The shifted reference has two sets in the
-  // workspace, indexed like F below; shift(set, X) goes behind every linearisation launch, into the set that launch writes.
-  const bool with_cost = cost != nullptr && cost->kind != 0;
-  double *Xr[2] = {nullptr, nullptr};
-  unsigned *cost_bad = nullptr;
-  auto shift = [&](int set, const double *X) {  // (inside the linearisation's ProfScope: timed in class 6 with it)
-    if (!with_cost) return;
-    launch_obstacle_ref_shift(*cost, x, N, M, X, p0->Q, p0->X_ref, Xr[set], cost_bad, c->stream);
-  };
-  // trajectory buffers A = (X_prev, U_prev), B = (X_out, U_out); linearisation buffers 0 = (f, fx, fu), 1 = (f2, fx2, fu2)
-  double *XA = const_cast<double *>(p0->X_prev), *UA = const_cast<double *>(p0->U_prev), *XB = p0->X_out, *UB = p0->U_out;
-  double *F[2][3] = {{const_cast<double *>(p0->f), const_cast<double *>(p0->fx), const_cast<double *>(p0->fu)}, {f2, fx2, fu2}};
-  // Built-in constraint (keepout.hip): the sub-problem runs at xd = x + K states on the caller's augmented buffers, of which the
-  // iterate-dependent ones have two sets, indexed like F; augment(set, X) goes behind every linearisation launch and its shift.  The
-  // trajectory pairs stay at x: the sub-problem's states land in aug->X_out and the follow-up strips them into the pair.
-  const bool with_cstr = cstr != nullptr && cstr->kind != 0;
-  const int K = with_cstr ? cstr->K : 0;
-  auto augment = [&](int set, const double *X) {  // (the reference it extends: this iteration's shifted one, else the caller's)
-    if (!with_cstr) return;
-    launch_keepout_augment(*cstr, x, u, N, M, X, F[set][0], F[set][1], F[set][2], with_cost ? Xr[set] : p0->X_ref, aug->f[set], aug->fx[set], aug->fu[set], aug->X_prev[set],
-                           aug->X_ref[set], aug->xu[set], c->stream);
-  };
-  const bool soc = p0->soc_u_interior != nullptr || p0->cone_count > 0;
-  const bool cone_obj = (p0->flags & PMPC_CONE_OBJECTIVE) != 0;  // the sub-problem is the reference's default path (c_lcone_solve)
-  const int jac32 = (p0->flags & PMPC_F32_MATRICES) ? 1 : 0;  // (f / fx / fu scratch sets: fx, fu FLOAT arrays then)
-  // Compact Jacobian records (jac_compact.h) instead of the dense fx / fu — a third of the bytes of the one kernel of the step that is
-  // bound by its write stream — whenever the coming solve is expected to be a warm attempt of the active-set rounds without a rollout
-  // (QpSolve::as_start, use_defect), whose sweeps read the records as they are; a solve that takes another turn expands them first
-  // (QpSolve::densify).  PMPC_LIN_COMPACT=0 switches them off (A/B).  Never with a constraint: the augmentation reads dense Jacobians.
-  static const bool lin_compact_env = !(getenv("PMPC_LIN_COMPACT") && atoi(getenv("PMPC_LIN_COMPACT")) == 0);
-  const bool compact_ok = lin_compact_env && !with_cstr && !cone_obj && !jac32 && !c->multi() && p0->Nc >= 0 && p0->Nc <= 1 &&
-                          jac_compact_dims(model, x, u) && (p0->flags & PMPC_SYMMETRIC_COST) &&
-                          !(p0->flags & (PMPC_HAS_SLEW | PMPC_HAS_SLEW0 | PMPC_FORCE_GENERIC | PMPC_COLD_START)) &&
-                          ((p0->flags & PMPC_HAS_UBOUNDS) || soc) && !(p0->barrier_mu > 0.0) && c->opt[OPT_AS_DEFECT] != 0.0 &&
-                          c->opt[OPT_AS_WARM] != 0.0 && c->opt[OPT_POLISH_MU] > 0.0;
-  bool compact_set[2] = {false, false};  // what the linearisation buffer sets hold
-  int done = 0, cur = 0;
-  // (likewise refused: a cost description the kernels cannot run, and a cost next to fp32-stored matrices — the shift reads Q as doubles;
-  //  a constraint description the kernels cannot run, incomplete augmented buffers, and a constraint next to what rows on the states are
-  //  not solved with: a stage cone, slew penalties, fp32-stored matrices, a sharded context, the squareplus smoothing of the boxes)
-  const bool cstr_refused = with_cstr && (!keepout_cstr_valid(cstr, x) || !keepout_strip_dims_valid(p0->xdim, K, p0->udim) || !scp_aug_complete(aug) || soc ||
-                                          (p0->flags & (PMPC_HAS_SLEW | PMPC_HAS_SLEW0)) || jac32 || c->multi() || p0->smooth_cstr == 1);
-  // (and a runtime-compiled model whose dimensions are not the problem's, or next to fp32-stored matrices: its Jacobians are doubles)
-  bool custom_refused = false;
-  if (model_custom(model)) {
-    int mx = 0, mu = 0;
-    custom_refused = jac32 || !custom_model_dims(model, &mx, &mu) || mx != x || mu != u;
-  }
-  if (!model_known(c, model) || custom_refused || (with_cost && (jac32 || !obstacle_cost_valid(cost, x))) || cstr_refused) {  // nothing runs (the kernels of some other model would read the caller's arrays with ITS dimensions)
-    if (infos && steps > 0) { memset(&infos[0], 0, sizeof(pmpc_info)); infos[0].status = 2; }
-    if (last_in_out) *last_in_out = 0;
-    return 0;
-  }
-  bool lin_ready = false;  // the linearisation of iteration `done` is already enqueued (valid speculation of the previous one)
-  try {
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipMemsetAsync(res, 0, (size_t)steps * sizeof(double), c->stream));  // (the residual kernel takes a maximum into its slot)
-    if (with_cost) {
-      for (DevBuf &b : c->ws.cost_ref) b.ensure((size_t)p0->M * p0->N * p0->xdim * sizeof(double));
-      Xr[0] = c->ws.cost_ref[0].d(); Xr[1] = c->ws.cost_ref[1].d();
-      cost_bad = cost_bad_counter(c);
-    }
-    for (; done < steps; done++) {
-      double *Xp = (done & 1) ? XB : XA, *Up = (done & 1) ? UB : UA, *Xo = (done & 1) ? XA : XB, *Uo = (done & 1) ? UA : UB;
-      if (!lin_ready) {
-        ProfScope ps(c, 6);
-        compact_set[cur] = compact_ok && (done > 0 || !first_cold);
-        if (compact_set[cur])
-          launch_linearize_compact(model, N, M, p0->x0, Xp, Up, params, F[cur][0], F[cur][1], nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream);
-        else
-          launch_linearize(model, N, M, p0->x0, Xp, Up, params, F[cur][0], F[cur][1], F[cur][2], c->stream, jac32);
-        shift(cur, Xp);
-        augment(cur, Xp);
-      }
-      p.f = F[cur][0]; p.fx = F[cur][1]; p.fu = F[cur][2];
-      if (with_cost) p.X_ref = Xr[cur];
-      c->jac_compact_fx = compact_set[cur] ? F[cur][1] : nullptr;
-      c->jac_compact_model = model;
-      p.X_prev = Xp; p.U_prev = Up; p.X_out = Xo; p.U_out = Uo;
-      p.flags = p0->flags | PMPC_STATIC_CONS_BOUNDS;
-      if (done > 0 || !first_cold) p.flags |= PMPC_PREV_IS_LAST_SOLUTION;
-      else p.flags &= ~(unsigned)PMPC_PREV_IS_LAST_SOLUTION;
-      if (with_cstr) {  // the restated problem: rows on the states as upper bounds on the K auxiliary states
-        p.xdim = (size_t)(x + K);
-        p.f = aug->f[cur]; p.fx = aug->fx[cur]; p.fu = aug->fu[cur]; p.X_prev = aug->X_prev[cur];
-        p.X_ref = (with_cost || p0->X_ref) ? aug->X_ref[cur] : nullptr;
-        p.Q = aug->Q; p.x0 = aug->x0; p.lx = aug->lx; p.ux = aug->xu[cur]; p.X_out = aug->X_out;
-        // X_prev~ holds zeros where the last output holds the rows' values: the flag's promise does not hold for the augmented arrays
-        p.flags = (p.flags | PMPC_HAS_XBOUNDS) & ~(unsigned)PMPC_PREV_IS_LAST_SOLUTION;
-      }
-      bool res_dirty = false;  // the slot was zeroed with all the others when the loop started; a repeat must zero it again
-      auto follow_up = [&, Xp, Up, Xo, Uo](bool with_next_lin) {  // residual of this iteration (+ the next linearisation)
-        const bool next = with_next_lin && done + 1 < steps;
-        if (with_cstr) {  // the strip comes first: the residual and the next linearisation read the stripped states
-          {
-            ProfScope ps(c, 7);
-            launch_keepout_strip_residual(aug->X_out, Xo, Xp, Uo, Up, (long long)M * (long long)N, x, K, u, res + done, c->stream, res_dirty);
-            res_dirty = true;
-          }
-          if (next) {
-            ProfScope ps(c, 6);
-            compact_set[cur ^ 1] = false;
-            launch_linearize(model, N, M, p0->x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], c->stream, jac32);
-            shift(cur ^ 1, Xo);
-            augment(cur ^ 1, Xo);
-          }
-          return;
-        }
-        if (next && !res_dirty && !c->multi()) {  // both in ONE launch (independent work)
-          ProfScope ps(c, 6);
-          compact_set[cur ^ 1] = compact_ok;
-          if (compact_ok)
-            launch_linearize_compact(model, N, M, p0->x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], Xo, Xp, Uo, Up, x, u, res + done, c->stream);
-          else
-            launch_linearize_with_residual(model, N, M, p0->x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], Xo, Xp, Uo, Up, x, u,
-                                           res + done, c->stream, jac32);
-          shift(cur ^ 1, Xo);
-          res_dirty = true;
-          return;
-        }
-        {
-          ProfScope ps(c, 7);
-          launch_scp_residual(Xo, Xp, Uo, Up, (long long)M * (long long)N, x, u, res + done, c->stream, res_dirty);
-          res_dirty = true;
-        }
-        if (c->multi()) allreduce(c, res + done, 1, ncclFloat64, ncclMax);
-        if (next) {
-          ProfScope ps(c, 6);
-          compact_set[cur ^ 1] = compact_ok;
-          if (compact_ok)
-            launch_linearize_compact(model, N, M, p0->x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, c->stream);
-          else
-            launch_linearize(model, N, M, p0->x0, Xo, Uo, params, F[cur ^ 1][0], F[cur ^ 1][1], F[cur ^ 1][2], c->stream, jac32);
-          shift(cur ^ 1, Xo);
-        }
-      };
-      c->spec_fired = c->spec_ok = false;
-      c->post_batch = [&]() { follow_up(true); };
-      pmpc_info inf;
-      const int st = cone_obj ? lcone_body(c, &p, p.barrier_mu > 0.0 ? 1.0 / p.barrier_mu : std::numeric_limits<double>::quiet_NaN(), &inf, 0)
-                              : solve_impl(c, &p, &inf, 0, soc);
-      c->post_batch = nullptr;
-      c->jac_compact_fx = nullptr;
-      if (infos) infos[done] = inf;
-      if (st != 0) {  // (the failed solve left NaN in ITS outputs: with a constraint the states of the pair are not among them)
-        if (with_cstr) launch_fill(Xo, std::numeric_limits<double>::quiet_NaN(), (long long)M * N * x, c->stream);
-        break;
-      }
-      if (c->spec_fired && c->spec_ok) {
-        lin_ready = true;  // residual and next linearisation are in flight behind the accepted rounds
-        g_follow_ups[0]++;
-      } else {
-        follow_up(false);  // (a speculative copy, if any, was computed from unfinished outputs: redone; the next linearisation
-        lin_ready = false;  //  is enqueued at the top of the next iteration, into the other buffer set)
-        g_follow_ups[1]++;
-      }
-      cur ^= 1;
-    }
-    HIP_CHECK(hipGetLastError());
-  } catch (const PmpcHipError &) {
-    c->post_batch = nullptr;
-    c->jac_compact_fx = nullptr;
-    if (infos && done < steps) { memset(&infos[done], 0, sizeof(pmpc_info)); infos[done].status = 2; }
-    fail_after_error(c, nullptr, nullptr);
-    // both trajectory pairs hold unfinished iterates now: NaN, as every single-solve entry does with its outputs (res[done..] is
-    // undefined); never throws
-    try {
-      const double nan = std::numeric_limits<double>::quiet_NaN();
-      const long long ex = (long long)M * N * x, eu = (long long)M * N * u;
-      for (double *b : {XA, XB}) if (b) launch_fill(b, nan, ex, c->stream);
-      for (double *b : {UA, UB}) if (b) launch_fill(b, nan, eu, c->stream);
-      if (with_cstr) launch_fill(aug->X_out, nan, (long long)M * N * (x + K), c->stream);
-      HIP_WARN(hipStreamSynchronize(c->stream));
-    } catch (...) {
-    }
-  }
-  if (last_in_out) *last_in_out = done & 1;
-  return done;
-}
-
-// -------------------------------------------------------------------------------------------------
-// cone path (c_lcone_solve): the epsilon-anchored epigraph objective as a sequence of weighted QPs
-// -------------------------------------------------------------------------------------------------
 }  // extern "C"

@@ -1131,9 +1131,9 @@ int lcone_body(pmpc_ctx *c, const pmpc_problem *p0, double smooth_alpha, pmpc_in
       c->cons_w_active = (need && ncv > 0) ? w.cons_w.d() : nullptr;
       bool fired_here = false;
       std::function<void()> orig;
-      if (c->post_batch) {
-        orig.swap(c->post_batch);
-        c->post_batch = [&]() {
+      if (c->scp.post_batch) {
+        orig.swap(c->scp.post_batch);
+        c->scp.post_batch = [&]() {
           fired_here = true;
           enqueue_check();
           orig();
@@ -1142,16 +1142,13 @@ int lcone_body(pmpc_ctx *c, const pmpc_problem *p0, double smooth_alpha, pmpc_in
       int st_;
       try {
         st_ = pmpc_lqp_solve_device(c, &qq, &inf, verbose > 1);
-      } catch (...) {
+      } catch (...) {  // (the hook record is emptied by the scope that filled it: ScpHookGuard)
         c->cons_w_active = nullptr;
-        c->post_batch = nullptr;
         throw;
       }
       c->cons_w_active = nullptr;
-      if (c->post_batch) {  // not fired (the solve did not go through a first batch of rounds): the caller's hook stays for a later solve
-        c->post_batch = nullptr;
-        c->post_batch.swap(orig);
-      }
+      // not fired (the solve did not go through a first batch of rounds): the caller's hook stays for a later solve
+      if (c->scp.post_batch) c->scp.post_batch.swap(orig);
       if (fired_here) hook_solve = n_solves;
       n_solves++;
       qq.flags &= ~(unsigned)PMPC_PREV_IS_LAST_SOLUTION;  // (later solves of this call start from the workspace's set and solution)
@@ -1160,7 +1157,7 @@ int lcone_body(pmpc_ctx *c, const pmpc_problem *p0, double smooth_alpha, pmpc_in
       ipm_total += inf.ipm_iters;
       last = inf;
       if (st_ != 0) return st_;
-      if (!(fired_here && c->spec_ok)) enqueue_check();  // (what the hook computed saw unfinished outputs, or there was no hook)
+      if (!(fired_here && c->scp.ok)) enqueue_check();  // (what the hook computed saw unfinished outputs, or there was no hook)
       if (epi_multi) {
         // sharded: all costs to every rank (one all-reduce of a zero-padded vector), the same check on the host everywhere
         gather(w.Jc.d(), J);
@@ -1265,7 +1262,7 @@ int lcone_body(pmpc_ctx *c, const pmpc_problem *p0, double smooth_alpha, pmpc_in
       if (st_ != 0) return finish(st_);
     }
     // work the caller enqueued behind the first batch of rounds (pmpc_scp_loop_device) saw the final outputs only if that solve was the last
-    if (c->spec_fired && hook_solve != n_solves - 1) c->spec_ok = false;
+    if (c->scp.fired && hook_solve != n_solves - 1) c->scp.ok = false;
     if (settled) {
       c->cone_lam = lam;
       c->cone_lam_key = lkey;

@@ -1,7 +1,9 @@
 // solver_internal.h — what the translation units of the host side share: the context (pmpc_ctx), its workspace, the option table's
 // indices, and the helpers every solve path uses (collectives, device-published scalars, the structured Newton solve).
-//   solver.hip       contexts / options / communicators / profiling, the structured Newton solve, the fp32-storage protocol and the
-//                    slew increment form around the QP path, the SCP loop
+//   solver.hip       contexts / options / profiling, the structured Newton solve, the thin device entries, the fp32-storage protocol
+//                    and the slew increment form around the QP path
+//   comm.hip         communicators (RCCL bound lazily, the tests' in-process stand-in) and the two collectives
+//   solver_scp.hip   the SCP loop (pmpc_scp_loop_device*): one ScpLoop object per call, one method per phase
 //   solver_qp.hip    the QP path itself (solve_impl_body): one QpSolve object per solve, one method per phase
 //   solver_cone.hip  the cone objective (c_lcone_solve semantics): hard boxes, smoothed boxes, free particles, particle costs
 //   solver_host.hip  the host-pointer drop-in entry points (c_lqp_solve, c_lcone_solve and their extensions)
@@ -15,6 +17,7 @@
 #include <condition_variable>
 #include <cstring>
 #include <functional>
+#include <optional>
 #include <map>
 #include <atomic>
 #include <mutex>
@@ -162,21 +165,33 @@ struct pmpc_ctx {
   struct StagedChunk { void *dst; size_t bytes, off; };
   std::vector<StagedChunk> staged;  // what the bounce buffer (and the device staging buffers) hold from the previous call
   DevBuf host_flags;
-  // pmpc_scp_loop_device: work to enqueue right behind the first batch of active-set rounds, BEFORE the host waits for their
-  // outcome (the residual of this iteration and the linearisation of the next); spec_ok: that batch was the whole solve
-  std::function<void()> post_batch;
-  bool spec_fired = false, spec_ok = false;
-  // pmpc_scp_loop_device linearised the coming solve's Jacobians as compact records of this built-in model (jac_compact.h): they
-  // sit in this fx array and fu is stale.  The solve reads them as they are on the warm active-set path and expands them in place
-  // before anything else touches fx / fu (QpSolve::densify).  Null: fx / fu are the dense ABI stacks.
-  const double *jac_compact_fx = nullptr;
-  int jac_compact_model = 0;
+  // What an iteration of pmpc_scp_loop_device tells the solve it calls; empty outside one (ScpHookGuard).
+  struct ScpHook {
+    // work to enqueue right behind the first batch of active-set rounds, BEFORE the host waits for their outcome (the residual of this
+    // iteration and the linearisation of the next); the solve that enqueues it takes it out and sets `fired`; ok: that batch was the whole solve
+    std::function<void()> post_batch;
+    bool fired = false, ok = false;
+    // the loop linearised the coming solve's Jacobians as compact records of this built-in model (jac_compact.h): they sit in this
+    // fx array and fu is stale.  The solve reads them as they are on the warm active-set path and expands them in place before
+    // anything else touches fx / fu (QpSolve::densify, which nulls the pointer).  Null: fx / fu are the dense ABI stacks.
+    const double *compact_fx = nullptr;
+    int compact_model = 0;
+  } scp;
 };
 
 namespace pmpc_impl {
 
-void allreduce(pmpc_ctx *c, void *buf, size_t n, ncclDataType_t dt, ncclRedOp_t op);
+void allreduce(pmpc_ctx *c, void *buf, size_t n, ncclDataType_t dt, ncclRedOp_t op);  // comm.hip
 void broadcast(pmpc_ctx *c, void *buf, size_t n, ncclDataType_t dt, int root);
+void comm_release(pmpc_ctx *c);  // pmpc_destroy: the context's communicator
+unsigned *cost_bad_counter(pmpc_ctx *c);  // solver.hip: the workspace's counter of cost blocks the reference shift refused
+
+// The scope that fills pmpc_ctx::scp (an iteration of ScpLoop::run): the record is empty again when it ends, by return or by
+// exception — what the hook captures lives on the stack of that scope.
+struct ScpHookGuard {
+  pmpc_ctx *const c;
+  ~ScpHookGuard() { c->scp = pmpc_ctx::ScpHook{}; }
+};
 
 struct ProfScope {  // HIP events on the solver's own stream around one launch (bench.py's live kernel timing)
   pmpc_ctx *c;

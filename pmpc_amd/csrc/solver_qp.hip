@@ -138,7 +138,7 @@ int QpSolve::setup_workspace() {
   a.n = x + a.w;
   a.reg_x = p->reg_x; a.reg_u = p->reg_u;
   a.f = p->f; a.fx = p->fx; a.fu = p->fu; a.Q = p->Q; a.R = p->R;
-  a.jac_compact = (c->jac_compact_fx && c->jac_compact_fx == p->fx) ? c->jac_compact_model + 1 : 0;  // (the SCP loop linearised into compact records of that model: densify())
+  a.jac_compact = (c->scp.compact_fx && c->scp.compact_fx == p->fx) ? c->scp.compact_model + 1 : 0;  // (the SCP loop linearised into compact records of that model: densify())
   a.X_prev = p->X_prev; a.U_prev = p->U_prev; a.X_ref = p->X_ref; a.U_ref = p->U_ref;
   a.owner = (c->rank == 0);
   a.any_slew = (has_slew || has_slew0) ? 1 : 0;
@@ -247,13 +247,13 @@ void QpSolve::reset_scalars() {
 void QpSolve::densify() {
   if (!a.jac_compact) return;
   ProfScope ps(c, 5);
-  const int model = c->jac_compact_model;
+  const int model = c->scp.compact_model;
   const size_t bytes = (size_t)jac_compact_doubles(model, N, M) * D8;
   w.jac_tmp.ensure(bytes);
   HIP_CHECK(hipMemcpyAsync(w.jac_tmp.p, p->fx, bytes, hipMemcpyDeviceToDevice, s));
   launch_expand_jac(model, N, M, w.jac_tmp.d(), const_cast<double *>(p->fx), const_cast<double *>(p->fu), 0, s);
   a.jac_compact = 0;
-  c->jac_compact_fx = nullptr;
+  c->scp.compact_fx = nullptr;
   if (verbose) printf("pmpc_hip: compact Jacobian records expanded (the solve left the warm active-set path)\n");
 }
 
@@ -897,10 +897,10 @@ void QpSolve::as_rounds(AsAttempt &t) {
                       nullptr, b.as_viol, open_part);
       }
     }
-    if (round == 0 && c->post_batch) {  // the caller's follow-up work goes in behind the rounds before anything is read back
+    if (round == 0 && c->scp.post_batch) {  // the caller's follow-up work goes in behind the rounds before anything is read back
       std::function<void()> hook;
-      hook.swap(c->post_batch);
-      c->spec_fired = true;
+      hook.swap(c->scp.post_batch);
+      c->scp.fired = true;
       n_batches_at_hook = 0;
       hook();
     }
@@ -1084,7 +1084,7 @@ int QpSolve::as_accept(AsAttempt &t) {
   w.as_scale = dual_scale;
   w.as_count = nu;
   if (mode == 0) w.as_pred_rounds = round;
-  c->spec_ok = n_batches_at_hook == 1 && !(has_xb && !xbox);  // (with state boxes ignored, a second phase follows)  // what was enqueued behind the first batch saw the final outputs
+  c->scp.ok = n_batches_at_hook == 1 && !(has_xb && !xbox);  // (with state boxes ignored, a second phase follows)  // what was enqueued behind the first batch saw the final outputs
   return 0;
 }
 
