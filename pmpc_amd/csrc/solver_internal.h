@@ -5,7 +5,10 @@
 //   comm.hip         communicators (RCCL bound lazily, the tests' in-process stand-in) and the two collectives
 //   solver_scp.hip   the SCP loop (pmpc_scp_loop_device*): one ScpLoop object per call, one method per phase
 //   solver_qp.hip    the QP path itself (solve_impl_body): one QpSolve object per solve, one method per phase
-//   solver_cone.hip  the cone objective (c_lcone_solve semantics): hard boxes, smoothed boxes, free particles, particle costs
+//   solver_cone.hip  the cone objective (c_lcone_solve semantics) with hard boxes (lcone_body): one ConeSolve object per call — dispatch, the
+//                    epigraph path (its Epigraph), the rank-based iteration —, the free-particles body (one FreeParticles object), particle costs
+//   solver_cone_smooth.hip  the cone objective with smoothed boxes: the full-space Newton iteration (lcone_smooth_body)
+//   cone_common.h    what those bodies set up alike: sweep arguments, zero buffers, consensus horizon, triangle mirror, memory keys
 //   solver_host.hip  the host-pointer drop-in entry points (c_lqp_solve, c_lcone_solve and their extensions)
 #pragma once
 #include <dlfcn.h>
@@ -247,6 +250,11 @@ extern "C" {
 pmpc_problem widened_f32_problem(pmpc_ctx *c, const pmpc_problem *p, bool jacobians = true);  // solver.hip: fp32-stored matrix stacks widened for the fp64 paths
 void build_slew_increment_problem(pmpc_ctx *c, const pmpc_problem *p, pmpc_problem &q, SlewAug &g);  // solver.hip: slew penalties restated in control increments
 int lcone_body(pmpc_ctx *c, const pmpc_problem *p, double smooth_alpha, pmpc_info *info, int verbose);  // solver_cone.hip
+// solver_cone_smooth.hip: smoothed boxes (smode 0 log barrier, 1 squareplus of slope sbeta); -1 where it does not apply, else the status (info written)
+__attribute__((visibility("hidden"))) int lcone_smooth_body(pmpc_ctx *c, const pmpc_problem *p, double mu_b, pmpc_info *info, int verbose, int smode = 0, double sbeta = 1.0,
+                                                            bool phase1_start = false);
+int pmpc_epigraph_solve_host(int M, int nc, const double *J, const double *H, const double *g, const unsigned char *held, double K, double cap, double *lam_io, double *delta,
+                             double *t_out, int verbose);  // epigraph_host.hip
 int solve_impl_body(pmpc_ctx *c, const pmpc_problem *p, pmpc_info *info, int verbose, bool soc);  // solver_qp.hip: one sub-problem on the QP path
 bool slew_increment_form_applies(const pmpc_ctx *c, const pmpc_problem *p, bool soc);  // solver.hip
 int solve_slew_increment_form(pmpc_ctx *c, const pmpc_problem *p, pmpc_info *info, int verbose);  // solver.hip: calls solve_impl_body on the restated problem
