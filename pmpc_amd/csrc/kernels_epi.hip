@@ -1,4 +1,4 @@
-// kernels_epi.hip — elementwise passes of the cone objective WITH log-barrier smoothing (solver.hip, lcone_smooth_body).  gfx950 only.
+// kernels_epi.hip — elementwise passes of the cone objective WITH log-barrier smoothing (solver_cone_smooth.hip, SmoothSolve).  gfx950 only.
 //
 // Reference: PMPC.jl/src/main.jl:246-262 (smooth_cstr = "logbarrier": every box side becomes an exponential-cone row triple with a new
 // epigraph variable of cost 1, cone_utils.jl:173-203, i.e. the term -(1/alpha) log(alpha slack) in the objective) next to the

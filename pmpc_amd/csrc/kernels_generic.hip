@@ -1103,7 +1103,7 @@ int launch_cons_partials(const double *Hc_part, const double *gc_part, int M, in
   return G;
 }
 
-// Consensus weights (cone objective, solver.hip lcone_body): the sweeps run UNWEIGHTED — scaling a particle's whole cost leaves its
+// Consensus weights (cone objective, solver_cone.hip ConeSolve): the sweeps run UNWEIGHTED — scaling a particle's whole cost leaves its
 // gains, its active set and its conditional optimum given the shared controls unchanged — and the weights lambda_i enter only where
 // the particles meet:  sum_i lambda_i (H_i, g_i).  One elementwise pass writes lambda_i H_i, lambda_i g_i for the reductions; the terms
 // of the SHARED controls' box, which the owner's particle 0 carries on its diagonal / in its gradient (the 1e30 penalty of a held
@@ -1138,7 +1138,7 @@ void launch_cons_scale(const double *Hc_part, const double *gc_part, const doubl
                      with_H ? 1 : 0, outH, outg, as_act, as_big, Du, wu, u, owner);
 }
 
-// KKT check of the epigraph rows of the cone objective (solver.hip lcone_body) on the device: multipliers lam_i in [0, cap], particle
+// KKT check of the epigraph rows of the cone objective (solver_cone.hip ConeSolve) on the device: multipliers lam_i in [0, cap], particle
 // costs J_i (scaled by the caller's weights if any).  Threshold cost t = mean cost of the rows strictly inside (0, cap) (none: the midpoint
 // between the cheapest full row and the costliest empty one); violation = max over rows of  |J_i - t| (inside), t - J_i (full),
 // J_i - t (empty).  out = {violation, t, rows inside, 0}.  One block.

@@ -197,7 +197,8 @@ def test_sharded_cone_path_with_ties_matches_single_rank(world, copies, others, 
     assert np.all(Uw[:, :Nc] == Uw[0:1, :Nc])
 
 
-@pytest.mark.parametrize("world,copies,others,Nc,alpha,seed", [(2, 3, 3, 1, 10.0, 906), (4, 5, 3, 1, 10.0, 910), (2, 3, 3, 2, 10.0, 506), (4, 3, 5, 1, 100.0, 908)])
+@pytest.mark.parametrize("world,copies,others,Nc,alpha,seed", [(2, 3, 3, 1, 10.0, 906), (4, 5, 3, 1, 10.0, 910), (2, 3, 3, 2, 10.0, 506), (4, 3, 5, 1, 100.0, 908),
+                                                                 (2, 4, 2, -1, 10.0, 506)])  # (the last: Nc u = 12 > 8, the HOST Newton system's sharded table)
 def test_sharded_smoothed_cone_objective_matches_single_rank_and_direct_program(world, copies, others, Nc, alpha, seed):
     """Log-barrier smoothing of the cone objective (main.jl:246-262) on sharded particles: the Newton iteration's host side runs on gathered
     per-particle scalars and condensed blocks, identically on every rank; `copies` identical cheapest particles (a tie on the threshold, each with

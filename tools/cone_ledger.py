@@ -1,12 +1,17 @@
-"""The ledger of the cone objective's hard-box half (`lcone_body`, csrc/solver_cone.hip): which body answered a call and how many solves it
-took, as integers, on the smallest shape an existing test uses per dispatch.  Optima alone do not pin that: a dispatch that takes the
-wrong body, or one weighted solve too many, reaches the same optimum.
+"""The ledger of the cone objective (`ConeSolve` and its bodies, csrc/solver_cone.hip; the smoothed boxes' `SmoothSolve`,
+csrc/solver_cone_smooth.hip): which body answered a call and how many solves it took, as integers, on the smallest shape an existing test
+uses per dispatch — and, for the smoothed half, per branch of its Newton iteration: warm and cold second solves, remembered multipliers,
+consensus horizons on the device and on the host system, barrier weights that damp steps and move the hinge width, squareplus, the
+declined calls, phase 1 and the sharded gathers.  Optima alone do not pin that: a dispatch that takes the wrong body, or one weighted
+solve too many, reaches the same optimum.
 
 Per solve, from `DeviceSolver.last_info`: `status`, `fast_path`, `ipm_iters`, `structured_solves`, `outer_solves`, `active_set_rounds`.
 tests/golden/cone_ledger.json holds these (tests/test_cone_ledger_gpu.py compares them exactly); the SHA-256 of the X and U bytes of
 every solve of a configuration is printed only — a kernel change may move it, a host-side change must not.
 
-    python tools/cone_ledger.py [--out ledger.json] [config ...]
+    python tools/cone_ledger.py [--out ledger.json] [--verbose] [config ...]
+
+--verbose passes `verbose=True` to every solve: the library's trace of its iterations on stdout (the smoothed body prints every Newton step).
 """
 import argparse
 import hashlib
@@ -21,6 +26,7 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
 FIELDS = ("status", "fast_path", "ipm_iters", "structured_solves", "outer_solves", "active_set_rounds")
+_verbose = [False]  # main(): --verbose
 _group = [7300]  # ids of the in-process communicators (tests/test_multirank_gpu.py counts from 1000, tools/scp_loop_ledger.py from 7100)
 
 
@@ -64,6 +70,14 @@ def _one(name, args_kw, Nc=1, **run):
     return [dict(name=name, args=args_kw[0], kw=args_kw[1], Nc=Nc, **run)]
 
 
+_LOG10 = dict(smooth_alpha=10.0)  # the log barrier at the weight most tests use
+_PHASE1 = (1, 6, 2.0)  # rand_problem: seed, M, state bound (control bound 0.4); phase 1 ends with status 0, so does the solve
+
+
+def _squareplus(beta):
+    return dict(smooth_alpha=10.0, smooth_cstr="squareplus", smooth_beta=beta)
+
+
 # name -> the runs of the configuration: each one context (or `world` in-process ranks), `repeats` solves of one problem
 CONFIGS = {
     "tied_2_4_nc1": lambda: _forced(2, 4, 1, 0.4, 1231),
@@ -79,6 +93,34 @@ CONFIGS = {
     "tied_5_3_four_ranks": lambda: _one("solve", _tied(5, 3, 1, 0.4, 710), world=4, repeats=2),
     "logbarrier_3_3": lambda: _one("solve", _tied(3, 3, 1, 0.4, 907), solve=dict(smooth_alpha=10.0)),  # the dispatch into lcone_smooth_body
     "squareplus_one_particle_slew": lambda: _one("solve", _rand(74, 1, None, 0.5, None), solve=dict(smooth_alpha=10.0, smooth_cstr="squareplus", smooth_beta=2.0)),
+    # ---- the smoothed boxes' Newton iteration (SmoothSolve), branch by branch ----
+    # two solves on one context: warm start from the last solution, multipliers and hinge width remembered / not remembered / cold
+    "smooth_5_3_twice": lambda: _one("solve", _tied(5, 3, 1, 0.4, 1507), solve=_LOG10, repeats=2),
+    "smooth_5_3_twice_no_rank_memory": lambda: _one("solve", _tied(5, 3, 1, 0.4, 1507), solve=_LOG10, options={"cone_rank_memory": 0}, repeats=2),
+    "smooth_5_3_twice_cold": lambda: _one("solve", _tied(5, 3, 1, 0.4, 1507), solve=dict(_LOG10, cold_start=True), repeats=2),
+    # consensus horizons: Newton system on the device (Nc u = 4, off-diagonal blocks condensed), on the host (Nc u = 12), no shared control
+    "smooth_3_3_nc2": lambda: _one("solve", _tied(3, 3, 2, 0.4, 506), Nc=2, solve=_LOG10),
+    "smooth_4_2_ncN": lambda: _one("solve", _tied(4, 2, -1, 0.4, 506), Nc=-1, solve=_LOG10),
+    "smooth_nc0": lambda: _one("solve", _rand(501, 6), Nc=0, solve=_LOG10),
+    # barrier weights (tests/test_cone_ties_gpu.py, test_logbarrier_smoothing_with_ties): damped steps, width changes
+    "smooth_9_4_alpha1": lambda: _one("solve", _tied(9, 4, 1, 0.4, 2708), solve=dict(smooth_alpha=1.0)),
+    "smooth_3_3_alpha100": lambda: _one("solve", _tied(3, 3, 1, 0.4, 907), solve=dict(smooth_alpha=100.0)),
+    "squareplus_7": lambda: _one("solve", _rand(40, 7), solve=_squareplus(1.0)),
+    "squareplus_tied_3_3": lambda: _one("solve", _tied(3, 3, 1, 0.4, 41), solve=_squareplus(5.0)),
+    "squareplus_one_particle": lambda: _one("solve", _rand(71, 1), solve=_squareplus(2.0)),
+    "squareplus_one_weighted_particle": lambda: _one("solve", _rand(85, 1), weights=np.array([2.5]), solve=_squareplus(2.0)),
+    # declined by the smoothed body (-1): which body answers instead
+    "logbarrier_weights_declined": lambda: _one("solve", _rand(105, 6), weights=0.2 + np.random.default_rng(106).random(6), solve=_LOG10),
+    "logbarrier_slew_declined": lambda: _one("solve", _rand(75, 6, None, 0.5, None), solve=_LOG10),
+    # state boxes the rollout of the caller's controls leaves: phase 1 (the barrier QP), then the iteration from its controls
+    "smooth_phase1": lambda: _one("solve", _rand(*_PHASE1), solve=_LOG10),
+    "smooth_phase1_fails": lambda: _one("solve", _rand(0, 6, 1.0), solve=_LOG10),  # boxes the barrier QP cannot enter either: status 1, NaN outputs
+    # sharded (tests/test_multirank_gpu.py): the gathers of the costs, of the read-back after the direction, of the host system's table
+    "smooth_3_3_two_ranks": lambda: _one("solve", _tied(3, 3, 1, 0.4, 906), world=2, solve=_LOG10, repeats=2),
+    "smooth_5_3_four_ranks": lambda: _one("solve", _tied(5, 3, 1, 0.4, 910), world=4, solve=_LOG10, repeats=2),
+    "smooth_3_3_nc2_two_ranks": lambda: _one("solve", _tied(3, 3, 2, 0.4, 506), Nc=2, world=2, solve=_LOG10, repeats=2),
+    "smooth_4_2_ncN_two_ranks": lambda: _one("solve", _tied(4, 2, -1, 0.4, 506), Nc=-1, world=2, solve=_LOG10, repeats=2),
+    "squareplus_two_ranks": lambda: _one("solve", _tied(3, 5, 1, 0.4, 932), world=2, solve=_squareplus(5.0)),
 }
 
 
@@ -107,7 +149,7 @@ def _solves(s, args, kw, Nc, sl=slice(None), options=None, repeats=1, weights=No
         if sharded:
             opt["static_cons_bounds"] = rep > 0
         X, U, status = s.lcone_solve(f=dev(f), fx=T(fx), fu=T(fu), X_prev=dev(X_prev), U_prev=dev(U_prev), Q=T(Q), R=T(R), X_ref=dev(X_ref), U_ref=dev(U_ref),
-                                     reg_x=kw["reg_x"], reg_u=kw["reg_u"], Nc=Nc, symmetric_cost=True, **opt)
+                                     reg_x=kw["reg_x"], reg_u=kw["reg_u"], Nc=Nc, symmetric_cost=True, verbose=_verbose[0], **opt)
         s.sync()
         info = {k: int(s.last_info[k]) for k in FIELDS}
         assert info["status"] == status
@@ -177,7 +219,9 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("configs", nargs="*", default=list(CONFIGS), help="default: all")
     ap.add_argument("--out", help="write {config: ledger} as JSON")
+    ap.add_argument("--verbose", action="store_true", help="verbose=True for every solve: the library prints its iterations")
     a = ap.parse_args()
+    _verbose[0] = a.verbose
     ledgers = {}
     for name in a.configs:
         ledgers[name], digest = run_config(name)
