@@ -437,13 +437,20 @@ long long pmpc_ref_shift_bad_pivots(pmpc_ctx *ctx, int reset);
 /* A built-in cost for loops that have no Python callable.  kind 1, obstacles: K <= 16 Gaussian bumps shared by all particles,
  *   J_obs = sum_{i,j} sum_k w_k exp(-|x_ij[pos_idx] - c_jk|^2 / (2 sigma_k^2)),
  * x_ij = stage j (0-based: the state after j + 1 steps, row j of X_prev) of particle i; pos_idx: pos_dim = 2 or 3 state indices;
- * centres (device): (K, pos_dim) if per_stage = 0, (N, K, pos_dim) if 1 (moving obstacles); sigma, w (device): (K). */
+ * centres (device): (K, pos_dim) if per_stage = 0, (N, K, pos_dim) if 1 (moving obstacles); sigma, w (device): (K).
+ *
+ * kind 2, custom: a runtime-compiled stage cost loaded on the context (pmpc_cost_load below) — `id` its id, `uses_u` as it was compiled,
+ * `cparams` (device) its parameters (M, cdim).  The three members share the storage of K, pos_dim and centres, which kind 2 does not
+ * use: the struct keeps its size and the offsets of kind 1.  pmpc_obstacle_cost_grad_device / pmpc_obstacle_ref_shift_device answer
+ * kind 2 with 2. */
 typedef struct pmpc_scp_cost {
-  int kind; /* 0 none, 1 obstacles */
-  int K, pos_dim;
+  int kind; /* 0 none, 1 obstacles, 2 custom */
+  union { int K; int id; };
+  union { int pos_dim; int uses_u; };
   int pos_idx[3];
   int per_stage;
-  const double *centres, *sigma, *w;
+  union { const double *centres; const double *cparams; };
+  const double *sigma, *w;
 } pmpc_scp_cost;
 size_t pmpc_abi_scp_cost_size(void); /* sizeof(pmpc_scp_cost) as the library was built (see pmpc_abi_struct_sizes) */
 
@@ -465,6 +472,37 @@ int pmpc_obstacle_ref_shift_device(pmpc_ctx *ctx, const pmpc_scp_cost *cost, siz
 int pmpc_scp_loop_device_cost(pmpc_ctx *ctx, int model, const double *params, const pmpc_problem *p, double *f2, double *fx2,
                               double *fu2, int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out,
                               const pmpc_scp_cost *cost);
+
+/* Custom stage costs: J = sum over particles i and stages j of stage_cost(X[i,j], U[i,j], p_i, j, N), handed over as device code and
+ * compiled at run time like a custom model; the gradients (cx, cu) come from forward-mode dual numbers.  `source` is one function template,
+ *   template <class T> __device__ T stage_cost(const T *x, const T *u, const double *p, int j, int N);
+ * x[XD] = row j of X_prev, u[UD] = row j of U_prev (0-based stage j: the state after j + 1 steps and the control that led to it),
+ * p[CD] = this particle's cost parameters, with XD, UD, CD defined as macros in front of it.  T is double or a dual number with the
+ * operator and function set of the custom models (above).  p points into global memory (it is not copied per thread): CD may be 1 .. 64;
+ * XD, UD in 1 .. 16.  uses_u = 0 promises d/du == 0: cu is not formed, and the loops neither shift U_ref nor read R.
+ *   pmpc_cost_compile   as pmpc_model_compile (no context, no GPU): 0 / 1 bad argument / 2 no runtime compiler / 3 compile error;
+ *                       pmpc_model_free_code frees *code.
+ *   pmpc_cost_load      returns the cost's id >= PMPC_COST_CUSTOM0, or -1 / -2 / -3 as pmpc_model_load.  Costs have a table of their
+ *                       own: an id means a cost only where a cost is asked for, it is known to the context that loaded it, until
+ *                       pmpc_cost_unload (0; 2: not a cost id of this context) or pmpc_destroy.  A cost and a model are separate
+ *                       modules: unloading one leaves the other.
+ *   pmpc_custom_cost_grad_device   cx (M, N, xdim), cu (M, N, udim; NULL for a cost compiled with uses_u = 0, which never writes it),
+ *                       val (M, N) stage values or NULL, at (X_prev, U_prev), cparams (M, cdim): one launch, asynchronous on
+ *                       pmpc_stream().  0; 1 HIP error; 2 and nothing launched: id not of this context, null cx, null cu for a cost
+ *                       that uses u.
+ * In the pmpc_scp_loop_device family a kind-2 pmpc_scp_cost enqueues behind every linearisation launch (the speculative one included)
+ * the gradient kernel into one workspace scratch (cx | cu), pmpc_ref_shift on Q into the X_ref set of that launch and — unless uses_u
+ * is 0 — pmpc_ref_shift on R into a U_ref set kept the same way; p->X_ref / p->U_ref are not written; blocks of Q and R that are not
+ * positive definite count in pmpc_ref_shift_bad_pivots.  Refused before anything runs (0, infos[0].status = 2): an id that is not this
+ * context's, dimensions that are not the problem's, null cparams, PMPC_F32_MATRICES, and a null p->X_ref (or p->U_ref with uses_u):
+ * the shift reads the reference it moves. */
+#define PMPC_COST_CUSTOM0 1000
+int pmpc_cost_compile(const char *source, int xdim, int udim, int cdim, int uses_u, const char *arch, void **code, size_t *bytes, char *log,
+                      size_t log_cap);
+int pmpc_cost_load(pmpc_ctx *ctx, const void *code, size_t bytes, int xdim, int udim, int cdim, int uses_u);
+int pmpc_cost_unload(pmpc_ctx *ctx, int id);
+int pmpc_custom_cost_grad_device(pmpc_ctx *ctx, int id, size_t N, size_t M, const double *X_prev, const double *U_prev, const double *cparams,
+                                 double *cx, double *cu, double *val);
 
 /* A built-in constraint for loops that have no Python callable.  kind 1, keep-out: every stage j = 0 .. N-1 (0-based: the state after
  * j + 1 steps, row j of X_prev) of every particle i stays outside K balls, 1 <= K <= 4, in the position sub-space pos_idx (pos_dim = 2 or

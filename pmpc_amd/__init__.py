@@ -12,6 +12,7 @@ from .problem_struct import Problem  # noqa: F401
 from .problem_matrices import lqp_generate_problem_matrices  # noqa: F401
 from .extra_cstrs import keepout_augment, keepout_rows, make_keepout_extra_cstrs_fn  # noqa: F401
 from .custom_model import CustomModel  # noqa: F401
+from .custom_cost import CustomCost  # noqa: F401
 
 
 def scp_solve_device(*args, **kw):

@@ -35,8 +35,10 @@ ABI_SYMBOLS = [
     "pmpc_keepout_strip_residual_device", "pmpc_scp_loop_device_cstr", "pmpc_abi_scp_aug_size", "pmpc_scp_loop_follow_ups",
     "pmpc_shift_active_set_device", "pmpc_warm_shift_device", "pmpc_warm_set_read_device",
     "pmpc_model_compile", "pmpc_model_free_code", "pmpc_model_load", "pmpc_model_unload",
+    "pmpc_cost_compile", "pmpc_cost_load", "pmpc_cost_unload", "pmpc_custom_cost_grad_device",
 ]
 MODEL_CUSTOM0 = 1000  # PMPC_MODEL_CUSTOM0 (include/pmpc_abi.h): ids from here on are runtime-compiled models loaded on a context
+COST_CUSTOM0 = 1000  # PMPC_COST_CUSTOM0: ids of runtime-compiled stage costs (a table of their own)
 
 
 class PmpcProblem(ctypes.Structure):
@@ -58,10 +60,24 @@ class PmpcInfo(ctypes.Structure):
                 ("max_violation", ctypes.c_double), ("outer_solves", ctypes.c_int), ("active_set_rounds", ctypes.c_int)]
 
 
+class _KOrId(ctypes.Union):
+    _fields_ = [("K", ctypes.c_int), ("id", ctypes.c_int)]
+
+
+class _PosDimOrUsesU(ctypes.Union):
+    _fields_ = [("pos_dim", ctypes.c_int), ("uses_u", ctypes.c_int)]
+
+
+class _CentresOrCparams(ctypes.Union):
+    _fields_ = [("centres", ctypes.c_void_p), ("cparams", ctypes.c_void_p)]
+
+
 class PmpcScpCost(ctypes.Structure):
-    """pmpc_scp_cost (include/pmpc_abi.h): the built-in cost of pmpc_scp_loop_device_cost."""
-    _fields_ = [("kind", ctypes.c_int), ("K", ctypes.c_int), ("pos_dim", ctypes.c_int), ("pos_idx", ctypes.c_int * 3), ("per_stage", ctypes.c_int),
-                ("centres", ctypes.c_void_p), ("sigma", ctypes.c_void_p), ("w", ctypes.c_void_p)]
+    """pmpc_scp_cost (include/pmpc_abi.h): the cost of pmpc_scp_loop_device_cost — kind 1 the built-in obstacles, kind 2 a loaded custom
+    cost, whose id / uses_u / cparams share the storage of K / pos_dim / centres."""
+    _anonymous_ = ("_a", "_b", "_c")
+    _fields_ = [("kind", ctypes.c_int), ("_a", _KOrId), ("_b", _PosDimOrUsesU), ("pos_idx", ctypes.c_int * 3), ("per_stage", ctypes.c_int),
+                ("_c", _CentresOrCparams), ("sigma", ctypes.c_void_p), ("w", ctypes.c_void_p)]
 
 
 class PmpcScpCstr(ctypes.Structure):
@@ -224,6 +240,15 @@ def load():
         lib.pmpc_model_load.restype = ctypes.c_int
         lib.pmpc_model_unload.argtypes = [vp, ctypes.c_int]
         lib.pmpc_model_unload.restype = ctypes.c_int
+    if hasattr(lib, "pmpc_cost_compile"):  # (likewise: runtime-compiled stage costs)
+        lib.pmpc_cost_compile.argtypes = [ctypes.c_char_p] + [ctypes.c_int] * 4 + [ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.c_char_p, sz]
+        lib.pmpc_cost_compile.restype = ctypes.c_int
+        lib.pmpc_cost_load.argtypes = [vp, ctypes.c_char_p, sz] + [ctypes.c_int] * 4
+        lib.pmpc_cost_load.restype = ctypes.c_int
+        lib.pmpc_cost_unload.argtypes = [vp, ctypes.c_int]
+        lib.pmpc_cost_unload.restype = ctypes.c_int
+        lib.pmpc_custom_cost_grad_device.argtypes = [vp, ctypes.c_int, sz, sz] + [vp] * 6
+        lib.pmpc_custom_cost_grad_device.restype = ctypes.c_int
     lib.pmpc_version.argtypes = []
     lib.pmpc_version.restype = ctypes.c_char_p
     # layout check: the library's structs against this binding's mirrors (include/pmpc_abi.h: pmpc_abi_struct_sizes)

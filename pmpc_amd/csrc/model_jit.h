@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <string>
+
 #include "../../include/pmpc_abi.h"
 
 inline bool model_custom(int model) { return model >= PMPC_MODEL_CUSTOM0; }
@@ -16,3 +18,11 @@ void custom_launch_linearize(int model, int N, int M, const double *x0, const do
 void custom_launch_rollout(int model, int N, int M, const double *x0, const double *U, const double *params, double *X, hipStream_t s);
 void custom_launch_shift_plan(int model, int N, int M, int sh, const double *X, const double *U, const double *params, const double *U_tail,
                               double *Xn, double *Un, double *um1n, hipStream_t s);
+
+// The runtime compile that models and costs (cost_jit.hip) share: `program` with `nheaders` in-memory headers for the target id `arch`
+// (a feature suffix is dropped).  0: *code (malloc'd) holds *bytes; 1 bad arch; 2 no runtime compiler; 3 compile error; the
+// compiler's text goes to log.  `who` / `what`: the entry point and its subject, for the messages.
+int jit_compile(const char *who, const char *what, const std::string &program, const char *program_name, int nheaders, const char *const *headers,
+                const char *const *names, const char *arch, void **code, size_t *bytes, char *log, size_t log_cap);
+void jit_write_log(char *log, size_t cap, const std::string &text);
+const char *jit_dual_header();  // the text of model_dual.h

@@ -6,6 +6,7 @@
 //     #include "model_dual.h"        (the dual arithmetic: the file of that name, wrapped into model_dual.inc by the Makefile)
 //     <the user's `template <class T> __device__ void step(const T *x, const T *u, const double *p, T *xn)`>
 //     #include "model_kernels.h"     (pmpc_jit_linearize / _rollout / _shift_plan over step<>; likewise model_kernels.inc)
+// jit_compile is the runtime compile itself, shared with the custom stage costs (cost_jit.hip).
 // Compiling needs neither a context nor a GPU.  Loading puts the code object on a context's device; the loaded models of the process
 // sit in one table keyed by id, each entry owned by the context it was loaded on: an id is known to that context only, and
 // pmpc_destroy unloads what the context still owns.  The kernels are launched with hipModuleLaunchKernel on the caller's stream.
@@ -103,6 +104,61 @@ void write_log(char *log, size_t cap, const std::string &text) {
 
 }  // namespace
 
+const char *jit_dual_header() { return kDualHeader; }
+
+void jit_write_log(char *log, size_t cap, const std::string &text) { write_log(log, cap, text); }
+
+// The runtime compile, written once for models and costs: the target-id check, the lazily bound compiler, create / compile / log /
+// code object / destroy.  `who` names the entry in the messages, `what` what needs the compiler.  *code is malloc'd.
+int jit_compile(const char *who, const char *what, const std::string &program, const char *program_name, int nheaders, const char *const *headers,
+                const char *const *names, const char *arch, void **code, size_t *bytes, char *log, size_t log_cap) {
+  const std::string me(who);
+  std::string target(arch);
+  target = target.substr(0, target.find(':'));  // the target id alone: no feature suffix (never an xnack+ code object)
+  if (target.empty() || target.find_first_not_of("abcdefghijklmnopqrstuvwxyz0123456789") != std::string::npos) {
+    write_log(log, log_cap, me + ": arch must be a target id such as gfx950");
+    return 1;
+  }
+  std::lock_guard<std::mutex> lk(g_rtc_mutex);
+  if (!g_rtc.load()) {
+    write_log(log, log_cap, me + ": libhiprtc.so could not be loaded: " + what + " need the HIP runtime compiler");
+    return 2;
+  }
+  hiprtcProgram prog = nullptr;
+  if (g_rtc.CreateProgram(&prog, program.c_str(), program_name, nheaders, headers, names) != HIPRTC_SUCCESS) {
+    write_log(log, log_cap, me + ": hiprtcCreateProgram failed");
+    return 2;
+  }
+  const std::string opt_arch = "--offload-arch=" + target;
+  const char *opts[] = {opt_arch.c_str(), "-O3", "-std=c++17"};
+  const hiprtcResult rc = g_rtc.CompileProgram(prog, 3, opts);
+  size_t ln = 0;
+  std::string text;
+  if (g_rtc.GetProgramLogSize(prog, &ln) == HIPRTC_SUCCESS && ln > 1) {
+    text.resize(ln);
+    if (g_rtc.GetProgramLog(prog, &text[0]) != HIPRTC_SUCCESS) text.clear();
+  }
+  int ret = 0;
+  if (rc != HIPRTC_SUCCESS) {
+    write_log(log, log_cap, text.empty() ? me + ": hiprtcCompileProgram failed without a log" : text);
+    ret = 3;
+  } else {
+    write_log(log, log_cap, text);  // (warnings, if any)
+    size_t n = 0;
+    char *buf = nullptr;
+    if (g_rtc.GetCodeSize(prog, &n) != HIPRTC_SUCCESS || n == 0 || !(buf = (char *)malloc(n)) || g_rtc.GetCode(prog, buf) != HIPRTC_SUCCESS) {
+      free(buf);
+      write_log(log, log_cap, me + ": the compiler returned no code object");
+      ret = 2;
+    } else {
+      *code = buf;
+      *bytes = n;
+    }
+  }
+  g_rtc.DestroyProgram(&prog);
+  return ret;
+}
+
 bool model_known(const pmpc_ctx *c, int model) {
   if (!model_custom(model)) return model_known(model);
   JitModel m;
@@ -163,54 +219,11 @@ int pmpc_model_compile(const char *source, int xdim, int udim, int pdim, const c
     write_log(log, log_cap, "pmpc_model_compile: xdim, udim and pdim must be in 1 .. 16");
     return 1;
   }
-  std::string target(arch);
-  target = target.substr(0, target.find(':'));  // the target id alone: no feature suffix (never an xnack+ code object)
-  if (target.empty() || target.find_first_not_of("abcdefghijklmnopqrstuvwxyz0123456789") != std::string::npos) {
-    write_log(log, log_cap, "pmpc_model_compile: arch must be a target id such as gfx950");
-    return 1;
-  }
-  std::lock_guard<std::mutex> lk(g_rtc_mutex);
-  if (!g_rtc.load()) {
-    write_log(log, log_cap, "pmpc_model_compile: libhiprtc.so could not be loaded: custom models need the HIP runtime compiler");
-    return 2;
-  }
   const std::string program = "#define XD " + std::to_string(xdim) + "\n#define UD " + std::to_string(udim) + "\n#define PD " + std::to_string(pdim) +
                               "\n#define PMPC_JIT_UNITS " + std::to_string(lin_units(xdim, udim)) + "\n#include \"model_dual.h\"\n#line 1 \"step\"\n" +
                               source + "\n#include \"model_kernels.h\"\n";
   const char *headers[] = {kDualHeader, kKernelsHeader}, *names[] = {"model_dual.h", "model_kernels.h"};
-  hiprtcProgram prog = nullptr;
-  if (g_rtc.CreateProgram(&prog, program.c_str(), "pmpc_custom_model.hip", 2, headers, names) != HIPRTC_SUCCESS) {
-    write_log(log, log_cap, "pmpc_model_compile: hiprtcCreateProgram failed");
-    return 2;
-  }
-  const std::string opt_arch = "--offload-arch=" + target;
-  const char *opts[] = {opt_arch.c_str(), "-O3", "-std=c++17"};
-  const hiprtcResult rc = g_rtc.CompileProgram(prog, 3, opts);
-  size_t ln = 0;
-  std::string text;
-  if (g_rtc.GetProgramLogSize(prog, &ln) == HIPRTC_SUCCESS && ln > 1) {
-    text.resize(ln);
-    if (g_rtc.GetProgramLog(prog, &text[0]) != HIPRTC_SUCCESS) text.clear();
-  }
-  int ret = 0;
-  if (rc != HIPRTC_SUCCESS) {
-    write_log(log, log_cap, text.empty() ? std::string("pmpc_model_compile: hiprtcCompileProgram failed without a log") : text);
-    ret = 3;
-  } else {
-    write_log(log, log_cap, text);  // (warnings, if any)
-    size_t n = 0;
-    char *buf = nullptr;
-    if (g_rtc.GetCodeSize(prog, &n) != HIPRTC_SUCCESS || n == 0 || !(buf = (char *)malloc(n)) || g_rtc.GetCode(prog, buf) != HIPRTC_SUCCESS) {
-      free(buf);
-      write_log(log, log_cap, "pmpc_model_compile: the compiler returned no code object");
-      ret = 2;
-    } else {
-      *code = buf;
-      *bytes = n;
-    }
-  }
-  g_rtc.DestroyProgram(&prog);
-  return ret;
+  return jit_compile("pmpc_model_compile", "custom models", program, "pmpc_custom_model.hip", 2, headers, names, arch, code, bytes, log, log_cap);
 }
 
 void pmpc_model_free_code(void *code) { free(code); }

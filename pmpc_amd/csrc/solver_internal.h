@@ -75,6 +75,7 @@ struct Workspace {
   DevBuf xb_z, xb_st, xb_D, xb_g;  // state boxes inside the active-set rounds (kernels_xbox.hip)
   DevBuf jac_tmp;  // compact Jacobian records copied aside while they are expanded into the caller's fx / fu (QpSolve::densify)
   DevBuf cost_ref[2];  // pmpc_scp_loop_device_cost: the shifted reference X_ref - Q^-1 cx, one per linearisation scratch set
+  DevBuf cost_uref[2], cost_grad;  // a kind-2 cost: U_ref - R^-1 cu, sets as cost_ref; the gradient scratch (cx | cu), one set
   DevBuf cost_bad;  // blocks pmpc_ref_shift_device refused (one unsigned counter; cost_lin.hip)
   DevBuf m64[4];  // fp32-storage mode: fx, fu, Q, R widened for the paths that run the fp64 kernels
   // warm start: the early interior-point iterate (mu <= 0.5) remembered from the previous solve of the same shape

@@ -6,6 +6,7 @@
 #include "cost_lin.h"
 #include "keepout.h"
 #include "model_jit.h"
+#include "cost_jit.h"
 
 static std::atomic<unsigned long long> g_follow_ups[2];  // iterations whose follow-up was taken as enqueued behind the rounds / enqueued after the solve
 
@@ -41,6 +42,10 @@ struct ScpLoop {
   // Built-in cost: the sub-problem of an iteration tracks X_ref - Q^-1 cx(X_prev).  The shifted reference has two sets in the
   // workspace (Xr), indexed like F below; the shift goes behind every linearisation launch, into the set that launch writes.
   const bool with_cost;
+  // Custom cost (kind 2, cost_jit.hip): behind every linearisation launch the gradient kernel writes (cx | cu) into one workspace scratch
+  // and launch_ref_shift makes Xr[set] = X_ref - Q^-1 cx and, unless the cost was compiled with uses_u = 0, Ur[set] = U_ref - R^-1 cu,
+  // which the sub-problem then tracks; with uses_u = 0 neither cu nor R is touched.
+  const bool custom_cost, cost_u;
   // Built-in constraint (keepout.hip): the sub-problem runs at xd = x + K states on the caller's augmented buffers, of which the
   // iterate-dependent ones have two sets, indexed like F; the augmentation goes behind every linearisation launch and its shift.  The
   // trajectory pairs stay at x: the sub-problem's states land in aug->X_out and the follow-up strips them into the pair.
@@ -59,7 +64,7 @@ struct ScpLoop {
   double *const F[2][3];
 
   // ---- state of the iteration ----
-  double *Xr[2] = {nullptr, nullptr};
+  double *Xr[2] = {nullptr, nullptr}, *Ur[2] = {nullptr, nullptr}, *cgrad = nullptr;
   unsigned *cost_bad = nullptr;
   bool compact_set[2] = {false, false};  // what the linearisation buffer sets hold
   int done = 0, cur = 0;
@@ -70,6 +75,7 @@ struct ScpLoop {
           double *res_, pmpc_info *infos_, const pmpc_scp_cost *cost_, const pmpc_scp_cstr *cstr_, const pmpc_scp_aug *aug_)
       : c(c_), model(model_), params(params_), p0(p), steps(steps_), first_cold(first_cold_), res(res_), infos(infos_), cost(cost_), cstr(cstr_),
         aug(aug_), x((int)p->xdim), u((int)p->udim), N((int)p->N), M((int)p->M), with_cost(cost_ != nullptr && cost_->kind != 0),
+        custom_cost(with_cost && cost_->kind == 2), cost_u(custom_cost && cost_->uses_u != 0),
         with_cstr(cstr_ != nullptr && cstr_->kind != 0), K(with_cstr ? cstr_->K : 0), soc(p->soc_u_interior != nullptr || p->cone_count > 0),
         cone_obj((p->flags & PMPC_CONE_OBJECTIVE) != 0), jac32((p->flags & PMPC_F32_MATRICES) ? 1 : 0),
         compact_ok(lin_compact_env() && !with_cstr && !cone_obj && !jac32 && !c_->multi() && p->Nc >= 0 && p->Nc <= 1 && jac_compact_dims(model_, x, u) &&
@@ -90,7 +96,15 @@ struct ScpLoop {
       if (jac32 || !custom_model_dims(model, &mx, &mu) || mx != x || mu != u) return true;
     }
     // (a cost description the kernels cannot run, and a cost next to fp32-stored matrices — the shift reads Q as doubles)
-    if (with_cost && (jac32 || !obstacle_cost_valid(cost, x))) return true;
+    if (with_cost && !custom_cost && (jac32 || !obstacle_cost_valid(cost, x))) return true;
+    // (a custom cost that is not this context's or not of the problem's dimensions, without parameters, next to fp32-stored matrices, or
+    //  without the reference its shift moves: launch_ref_shift reads ref, and the built-in cost's path does not define a null one either)
+    if (custom_cost) {
+      int cx_ = 0, cu_ = 0, uses = 0;
+      if (jac32 || !custom_cost_known(c, cost->id) || !custom_cost_dims(cost->id, &cx_, &cu_, nullptr, &uses) || cx_ != x || cu_ != u ||
+          (uses != 0) != cost_u || !cost->cparams || !p0->X_ref || (cost_u && !p0->U_ref))
+        return true;
+    }
     // (a constraint description the kernels cannot run, incomplete augmented buffers, and a constraint next to what rows on the states are
     //  not solved with: a stage cone, slew penalties, fp32-stored matrices, a sharded context, the squareplus smoothing of the boxes)
     return with_cstr && (!keepout_cstr_valid(cstr, x) || !keepout_strip_dims_valid(p0->xdim, K, p0->udim) || !scp_aug_complete(aug) || soc ||
@@ -114,7 +128,15 @@ struct ScpLoop {
                                      c->stream, jac32);
     else
       launch_linearize(model, N, M, p0->x0, X, U, params, f[0], f[1], f[2], c->stream, jac32);
-    if (with_cost) launch_obstacle_ref_shift(*cost, x, N, M, X, p0->Q, p0->X_ref, Xr[set], cost_bad, c->stream);
+    if (custom_cost) {
+      const long long rows = (long long)M * N;
+      double *cu = cost_u ? cgrad + rows * x : nullptr;
+      custom_launch_cost_grad(cost->id, N, M, X, U, cost->cparams, cgrad, cu, nullptr, c->stream);
+      launch_ref_shift(x, rows, p0->Q, cgrad, p0->X_ref, Xr[set], cost_bad, c->stream);
+      if (cost_u) launch_ref_shift(u, rows, p0->R, cu, p0->U_ref, Ur[set], cost_bad, c->stream);
+    } else if (with_cost) {
+      launch_obstacle_ref_shift(*cost, x, N, M, X, p0->Q, p0->X_ref, Xr[set], cost_bad, c->stream);
+    }
     if (with_cstr)  // (the reference it extends: this iteration's shifted one, else the caller's)
       launch_keepout_augment(*cstr, x, u, N, M, X, f[0], f[1], f[2], with_cost ? Xr[set] : p0->X_ref, aug->f[set], aug->fx[set], aug->fu[set],
                              aug->X_prev[set], aug->X_ref[set], aug->xu[set], c->stream);
@@ -125,6 +147,7 @@ struct ScpLoop {
     pmpc_problem p = *p0;
     p.f = F[set][0]; p.fx = F[set][1]; p.fu = F[set][2];
     if (with_cost) p.X_ref = Xr[set];
+    if (cost_u) p.U_ref = Ur[set];
     p.X_prev = Xp; p.U_prev = Up; p.X_out = Xo; p.U_out = Uo;
     p.flags = p0->flags | PMPC_STATIC_CONS_BOUNDS;
     if (warm_start) p.flags |= PMPC_PREV_IS_LAST_SOLUTION;
@@ -175,6 +198,15 @@ struct ScpLoop {
       for (DevBuf &b : c->ws.cost_ref) b.ensure((size_t)p0->M * p0->N * p0->xdim * sizeof(double));
       Xr[0] = c->ws.cost_ref[0].d(); Xr[1] = c->ws.cost_ref[1].d();
       cost_bad = cost_bad_counter(c);
+    }
+    if (custom_cost) {
+      const size_t rows = (size_t)p0->M * p0->N;
+      c->ws.cost_grad.ensure(rows * (p0->xdim + (cost_u ? p0->udim : 0)) * sizeof(double));
+      cgrad = c->ws.cost_grad.d();
+      if (cost_u) {
+        for (DevBuf &b : c->ws.cost_uref) b.ensure(rows * p0->udim * sizeof(double));
+        Ur[0] = c->ws.cost_uref[0].d(); Ur[1] = c->ws.cost_uref[1].d();
+      }
     }
     bool lin_ready = false;  // the linearisation of iteration `done` is already enqueued (valid speculation of the previous one)
     for (; done < steps; done++, cur ^= 1) {

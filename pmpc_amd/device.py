@@ -50,6 +50,7 @@ class DeviceSolver:
         self.rank, self.world = 0, 1
         self.last_info: Dict[str, float] = {}
         self._custom: Dict[int, object] = {}  # model id -> the CustomModel loaded under it (load_model)
+        self._costs: Dict[int, object] = {}  # cost id -> the CustomCost loaded under it (load_cost); a table apart from the models'
 
     # ---- runtime-compiled dynamics models (pmpc_amd/custom_model.py) -----------------------------------
     def load_model(self, cm) -> int:
@@ -84,6 +85,56 @@ class DeviceSolver:
         if params is not None and tuple(params.shape) != (M, cm.pdim):
             raise ValueError(f"{cm!r} (model {model}): params must be (M, pdim) = ({M}, {cm.pdim}), got {tuple(params.shape)}")
 
+    # ---- runtime-compiled stage costs (pmpc_amd/custom_cost.py) ---------------------------------------
+    def load_cost(self, cc) -> int:
+        """The cost id (>= 1000, in a table of its own: it means a cost only where a cost is asked for) of a `pmpc_amd.CustomCost` on
+        this solver: compiled for the device's architecture and loaded on first use, the same id from then on.  It is known to this
+        solver only and goes with `unload_cost` or `close`."""
+        self._need("pmpc_cost_load")
+        for cid, loaded in self._costs.items():
+            if loaded is cc:
+                return cid
+        arch = torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0]  # the target id alone, never a feature suffix
+        code = cc.compile(arch)
+        cid = self.lib.pmpc_cost_load(self.h, code, len(code), cc.xdim, cc.udim, cc.pdim, int(cc.uses_u))
+        if cid < _lib.COST_CUSTOM0:
+            raise RuntimeError(f"pmpc_cost_load failed ({cid}) for {cc!r}")
+        self._costs[cid] = cc
+        return cid
+
+    def unload_cost(self, cost: int) -> None:
+        self._costs.pop(int(cost), None)
+        if self.lib.pmpc_cost_unload(self.h, int(cost)) != 0:
+            raise ValueError(f"cost {cost} is not a custom cost loaded on this solver")
+
+    def custom_cost_grad(self, cost, X_prev, U_prev, cparams, value=False, cx=None, cu=None, wait_current_stream=True):
+        """(cx (M, N, x), cu (M, N, u)) — with `value` also val (M, N), the stage values — of a custom cost at (X_prev, U_prev) with the
+        parameters cparams (M, pdim): one launch of the kernel compiled from the user's `stage_cost`.  `cost`: a `pmpc_amd.CustomCost`
+        (loaded on first use) or the id of `load_cost`.  cu is None for a cost with uses_u=False.  `cx` / `cu`, and a tensor given as `value`: preallocated outputs."""
+        self._need("pmpc_custom_cost_grad_device")
+        cid = self.load_cost(cost) if not isinstance(cost, int) else int(cost)
+        cc = self._costs.get(cid)
+        if cc is None:
+            raise ValueError(f"cost {cid} is not a custom cost loaded on this solver")
+        M, N, x = X_prev.shape
+        u = U_prev.shape[-1]
+        assert U_prev.shape == (M, N, u), (X_prev.shape, U_prev.shape)
+        cc.check_problem(M, x, u, cparams)
+        dev = X_prev.device
+        cx = torch.empty((M, N, x), dtype=torch.float64, device=dev) if cx is None else cx
+        if cc.uses_u:
+            cu = torch.empty((M, N, u), dtype=torch.float64, device=dev) if cu is None else cu
+        else:
+            cu = None
+        val = value if torch.is_tensor(value) else (torch.empty((M, N), dtype=torch.float64, device=dev) if value else None)
+        assert cx.shape == (M, N, x) and (cu is None or cu.shape == (M, N, u))
+        self._before(wait_current_stream)
+        st = self.lib.pmpc_custom_cost_grad_device(self.h, cid, N, M, _p(X_prev), _p(U_prev), _p(cparams), _p(cx), _p(cu), _p(val))
+        self._after(wait_current_stream)
+        if st != 0:
+            raise RuntimeError(f"pmpc_custom_cost_grad_device failed ({st})")
+        return (cx, cu, val) if val is not None else (cx, cu)
+
     def set_option(self, key: str, value: float) -> None:
         """Per-context algorithm switch (include/pmpc_abi.h, pmpc_set_option): e.g. ``set_option("xbox_as", 0)``."""
         if self.lib.pmpc_set_option(self.h, key.encode(), float(value)) != 0:
@@ -99,7 +150,7 @@ class DeviceSolver:
         if getattr(self, "h", None):
             self.lib.pmpc_destroy(self.h)  # (unloads the custom models with everything else)
             self.h = None
-            self._custom = {}
+            self._custom, self._costs = {}, {}
 
     def __del__(self):
         try:
@@ -417,17 +468,33 @@ class DeviceSolver:
             self.check_bad_pivots("ref_shift")
         return out
 
-    def prepare_cost(self, cost, N, x, device="cuda"):
+    def prepare_cost(self, cost, N, x, device="cuda", M=None, u=None):
         """A handle of a built-in cost for repeated `obstacle_cost_grad` / `scp_loop` calls on (N stages, x states): the descriptor
-        and its device arrays, uploaded once.  Both methods take the handle wherever they take the dict."""
-        return self._scp_cost(cost, N, x, device)
+        and its device arrays, uploaded once.  Both methods take the handle wherever they take the dict.  dict(kind="custom", cost=,
+        params=) (pmpc_amd.CustomCost; needs M and u): the cost is loaded on this solver and params (M, pdim) uploaded; the handle's
+        second entry is [params on the device, the CustomCost]."""
+        return self._scp_cost(cost, N, x, device, M, u)
 
-    def _scp_cost(self, cost, N, x, device):
+    def _scp_cost(self, cost, N, x, device, M=None, u=None):
         """dict(kind="obstacles", pos_idx=, centres=, sigma=, w=) -> pmpc_scp_cost (+ the tensors it points to, to be kept alive);
-        a handle of `prepare_cost` passes through."""
+        dict(kind="custom", cost=, params=) -> a kind-2 descriptor; a handle of `prepare_cost` passes through."""
         self._need("pmpc_scp_loop_device_cost")
         if isinstance(cost, tuple):
             return cost
+        from .custom_cost import check_cost_dict, is_custom
+
+        if is_custom(cost):
+            self._need("pmpc_cost_load")
+            if M is None or u is None:
+                raise ValueError('a dict(kind="custom") cost needs the problem\'s M and udim (prepare_cost(cost, N, x, device, M=, u=))')
+            check_cost_dict(cost, M, x, u)  # (host side, before anything is loaded)
+            cc = cost["cost"]
+            cid = self.load_cost(cc)
+            cparams = torch.as_tensor(cost["params"], dtype=torch.float64).to(device).reshape(M, cc.pdim).contiguous()
+            if torch.is_tensor(cost["params"]) and cparams.data_ptr() == cost["params"].data_ptr():
+                cparams = cparams.clone()  # (the handle's array is its own: MPCController.set_cost_params writes it in place)
+            torch.cuda.current_stream(self.device).synchronize()  # (uploaded on the caller's stream; the kernels read it on the solver's)
+            return _lib.PmpcScpCost(kind=2, id=cid, uses_u=int(cc.uses_u), cparams=cparams.data_ptr()), [cparams, cc]
         from .dynamics import _obstacle_arrays
 
         pos_idx, cen, sigma, w = _obstacle_arrays(cost, N, _TorchF64(device))
@@ -545,7 +612,9 @@ class DeviceSolver:
         per-iteration residuals (device tensor), per-iteration info dicts, whether the final iterate is in (X_out, U_out)
         (else in (X_prev, U_prev)), iterations completed.  `cost=dict(kind="obstacles", pos_idx=, centres=, sigma=, w=)`: the built-in
         obstacle cost (`obstacle_cost_grad`) is linearised about every iterate and the sub-problem tracks X_ref - Q^-1 cx (float64 Q
-        with symmetric positive definite blocks; refused with status 2 next to float32 matrices).
+        with symmetric positive definite blocks; refused with status 2 next to float32 matrices).  `cost=dict(kind="custom",
+        cost=pmpc_amd.CustomCost, params=(M, pdim))`: the user's stage cost (`custom_cost_grad`); the sub-problem tracks X_ref - Q^-1 cx
+        and, unless the cost has uses_u=False, U_ref - R^-1 cu (R likewise).
         `cstr=`: a keep-out constraint, the dict of `prepare_cstr` or its handle, with `aug=pmpc_amd.device_problem.keepout_buffers(problem, K)`
         (two sets), allocated once by the caller: every iteration's sub-problem runs at x + K states on those buffers (`keepout_augment`'s
         launch in front of it, `strip_residual`'s behind it); everything this method takes and returns stays at x states.  Refused by
@@ -560,7 +629,7 @@ class DeviceSolver:
         M, N, x = kw["f"].shape
         self._check_custom(model, M, params=params)  # (dimensions that are not the problem's: the library refuses them, status 2)
         if cost is not None:
-            sc, keep = self._scp_cost(cost, N, x, f2.device)
+            sc, keep = self._scp_cost(cost, N, x, f2.device, M, kw["U_prev"].shape[-1])
         if cstr is not None:
             self._need("pmpc_scp_loop_device_cstr")
             if aug is None:
@@ -591,7 +660,7 @@ class DeviceSolver:
             del keep
         self._after(wait_current_stream)
         if cost is not None:
-            self.check_bad_pivots("scp_loop(cost=...): Q")
+            self.check_bad_pivots("scp_loop(cost=...): Q" + (" or R" if sc.kind == 2 else ""))
         out = [{k: getattr(infos[i], k) for k, _ in _lib.PmpcInfo._fields_} for i in range(min(done + 1, steps))]
         if out:
             self.last_info = out[min(done, steps) - 1] if done > 0 else out[0]

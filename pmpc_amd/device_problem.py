@@ -83,10 +83,11 @@ def _stage_cone(soc, settings, T, M, N, xdim, udim, Nc) -> Dict[str, Any]:
 def build_problem(Q, R, x0=None, X_ref=None, U_ref=None, X_prev=None, U_prev=None, x_l=None, x_u=None, u_l=None, u_u=None,
                   reg_x: float = 1e0, reg_u: float = 1e-2, slew_rate: Optional[float] = None, u0_slew=None,
                   solver_settings: Optional[Dict[str, Any]] = None, soc: Optional[Dict[str, Any]] = None, builtin_model=None, params=None,
-                  device="cuda", own_copies: bool = False, need_sym: Optional[str] = None) -> DeviceProblem:
+                  device="cuda", own_copies: bool = False, need_sym: Optional[str] = None, builtin_cost=None) -> DeviceProblem:
     """`own_copies`: the references, boxes and params are clones (a caller that writes them in place later, as `MPCController` does);
     otherwise they alias the caller's tensors wherever no conversion is needed.  `need_sym`: the subject of the refusal of Q / R blocks
-    that are not symmetric ("builtin_cost needs"); None: they are allowed."""
+    that are not symmetric ("builtin_cost needs"); None: they are allowed.  `builtin_cost`: a dict(kind="custom", cost=, params=) is checked
+    against the problem's dimensions here (pmpc_amd.custom_cost.check_cost_dict); any other cost passes."""
     dev = torch.device(device)
     T = lambda z: None if z is None else torch.as_tensor(np.asarray(z) if not torch.is_tensor(z) else z, dtype=torch.float64, device=dev)
     Q, R, x0 = T(Q), T(R), T(x0)
@@ -95,6 +96,10 @@ def build_problem(Q, R, x0=None, X_ref=None, U_ref=None, X_prev=None, U_prev=Non
         assert Q.ndim == 3 and R.ndim == 3
         Q, R, x0 = Q[None], R[None], x0[None]
     M, N, xdim, udim = Q.shape[0], Q.shape[1], Q.shape[-1], R.shape[-1]
+    if builtin_cost is not None:
+        from .custom_cost import check_cost_dict
+
+        check_cost_dict(builtin_cost, M, xdim, udim)
     own = (lambda t: t.clone()) if own_copies else (lambda t: t)
     vec = lambda z, d: own(T(z).reshape(M, N, d).contiguous())
     X_ref = torch.zeros((M, N, xdim), dtype=torch.float64, device=dev) if X_ref is None else vec(X_ref, xdim)

@@ -24,8 +24,9 @@ start iterate, and with it the linearisation point, holds particle 0's shifted c
 control-box statuses and the plan's controls only.  The multiplier memories of the stage cones (`cone_z`), the state rows (`xb_z` /
 `xb_st`) and the cone objective's epigraph rows are not, so `warm_shift=True` is refused next to the cone objective (`solver` other than
 the QP path, `smooth_alpha`), `soc=` / `extra_cstrs`, state boxes `x_l` / `x_u`, slew (`slew_rate`, `slew_reg`; their increment form
-restates the controls as states) and `keepout=` (its loop clears the promise the warm start rests on anyway).  `builtin_cost=` is
-allowed; without control boxes nothing is stored and every step stays cold.
+restates the controls as states) and `keepout=` (its loop clears the promise the warm start rests on anyway).  `builtin_cost=` (the obstacle
+cost, or `dict(kind="custom", cost=pmpc_amd.CustomCost, params=)`, whose parameters `set_cost_params` rewrites in place) is allowed;
+without control boxes nothing is stored and every step stays cold.
 
 `keepout=dict(pos_idx=, centres=, radius=)` is the hard keep-out constraint of `solve(..., device=..., builtin_cstr=...)` (1 to 4 balls in the
 position sub-space `pos_idx`; centres `(K, pos_dim)`, `(N, K, pos_dim)` per stage or `(M, N, K, pos_dim)` per particle and stage) carried
@@ -52,6 +53,7 @@ import torch
 
 from .device import DeviceSolver
 from .device_problem import build_problem, keepout_buffers
+from .custom_cost import check_cost_dict, is_custom
 from .custom_model import CustomModel
 from .dynamics import model_id
 
@@ -114,6 +116,7 @@ class MPCController:
             raise ValueError("MPCController: Q (M, N, x, x) and R (M, N, u, u)")
         if custom:  # dimensions and params that are not the model's: likewise before any device is touched
             builtin_model.check_problem(np.shape(Q)[0], np.shape(Q)[-1], np.shape(R)[-1], params)
+        check_cost_dict(builtin_cost, np.shape(Q)[0], np.shape(Q)[-1], np.shape(R)[-1])  # (a custom cost: likewise)
         if keepout is not None:  # a description the kernels cannot run: likewise before any device is touched
             from .extra_cstrs import _keepout_arrays
 
@@ -151,7 +154,8 @@ class MPCController:
         self._pairs = [(p.X_prev, p.U_prev), (mk(M, N, x), mk(M, N, u))]  # the two trajectory pairs of the loop (`reset` fills the first)
         self._lin = [mk(M, N, x), mk(M, N, x, x), mk(M, N, u, x), mk(M, N, x), mk(M, N, x, x), mk(M, N, u, x)]  # f, fx, fu; f2, fx2, fu2
         self._res = mk(64)
-        self._cost = s.prepare_cost(builtin_cost, N, x, dev) if builtin_cost is not None else None
+        self._cost = s.prepare_cost(builtin_cost, N, x, dev, M=M, u=u) if builtin_cost is not None else None
+        self._custom_cost = is_custom(builtin_cost)
         self._kw = dict(p.solve_kw(), x0=self._x0, X_ref=self.X_ref, U_ref=self.U_ref, **soc_kw)
         # the keep-out constraint: the descriptor with its device arrays (`set_keepout` writes them in place) and the augmented buffers
         # of the library loop, both made once; x0~ = [x0 | 0] is refreshed from x0 every step
@@ -221,6 +225,21 @@ class MPCController:
                 self._load(cen, centres)
             if radius is not None:
                 self._load(rad, radius)
+        s._after()
+
+    def set_cost_params(self, cparams):
+        """New parameters (M, pdim) of the custom cost (`builtin_cost=dict(kind="custom", ...)`), copied into the resident array on the
+        solver's stream: the next step's linearisations read them."""
+        if not self._custom_cost:
+            raise ValueError('MPCController.set_cost_params: the controller was built without builtin_cost=dict(kind="custom", ...)')
+        resident, cc = self._cost[1]
+        shape = tuple(cparams.shape) if hasattr(cparams, "shape") else np.shape(cparams)
+        if shape != tuple(resident.shape):
+            raise ValueError(f"{cc!r}: params must be (M, pdim) = {tuple(resident.shape)}, got {shape}")
+        s = self.solver
+        s._before()
+        with torch.cuda.stream(s.stream):
+            self._load(resident, cparams)
         s._after()
 
     # ---- one MPC step ----------------------------------------------------------------------------------------

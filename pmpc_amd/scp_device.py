@@ -19,7 +19,9 @@ descriptor is uploaded once before the loop, and the shifts' counter of refused 
 `(cx, cu)`, each a GPU tensor or None; the iteration then tracks `X_ref - Q^-1 cx`, `U_ref - R^-1 cu` (`DeviceSolver.ref_shift`, a HIP
 kernel; `Q` / `R` must be symmetric), while the `obj` column keeps the caller's references, as upstream (:404).
 `builtin_cost=dict(kind="obstacles", pos_idx=..., centres=..., sigma=..., w=...)` is the built-in obstacle cost
-(`pmpc_amd.dynamics.obstacle_cost`), evaluated and applied in one launch.
+(`pmpc_amd.dynamics.obstacle_cost`), evaluated and applied in one launch.  `builtin_cost=dict(kind="custom", cost=pmpc_amd.CustomCost,
+params=(M, pdim))` is the user's own stage cost, compiled at run time (csrc/cost_jit.hip): `DeviceSolver.custom_cost_grad` gives
+`(cx, cu)`, then `ref_shift` on `Q` and — unless the cost has `uses_u=False` — on `R`.
 
 `builtin_cstr=dict(kind="keepout", pos_idx=..., centres=..., radius=...)` is the built-in keep-out constraint: every stage of every
 particle stays outside 1 to 4 balls in the position sub-space `pos_idx` (centres `(K, pos_dim)`, `(N, K, pos_dim)` moving, or
@@ -41,6 +43,7 @@ from typing import Any, Callable, Dict, Optional
 
 import torch
 
+from .custom_cost import is_custom
 from .custom_model import CustomModel
 from .device import DeviceSolver
 from .device_problem import build_problem, keepout_buffers
@@ -93,7 +96,7 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
     t_start = time.time()
     with_costs = lin_cost_fn is not None or builtin_cost is not None
     p = build_problem(Q, R, x0, X_ref, U_ref, X_prev, U_prev, x_l, x_u, u_l, u_u, reg_x, reg_u, slew_rate, u0_slew, solver_settings, soc,
-                      builtin_model, params, dev, need_sym="lin_cost_fn / builtin_cost need" if with_costs else None)
+                      builtin_model, params, dev, need_sym="lin_cost_fn / builtin_cost need" if with_costs else None, builtin_cost=builtin_cost)
     M, N, xdim, udim, single = p.M, p.N, p.xdim, p.udim, p.single
     X_prev, U_prev = p.X_prev, p.U_prev
     T = lambda z: torch.as_tensor(z, dtype=torch.float64, device=dev)  # (lin_cost_fn's gradients)
@@ -109,7 +112,8 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
     if verbose:
         print(tp.make_header())
     # the built-in cost's descriptor and device arrays: made once, before the loop (nothing of it is uploaded inside)
-    cost_handle = s.prepare_cost(builtin_cost, N, xdim, dev) if builtin_cost is not None else None
+    cost_handle = s.prepare_cost(builtin_cost, N, xdim, dev, M=M, u=udim) if builtin_cost is not None else None
+    custom_cost = is_custom(builtin_cost)
     # the built-in constraint: descriptor, the augmented buffers and the parts of the augmented problem that do not change with the
     # iterate (Q~, x0~, the lower bounds, the first xdim upper bounds) — made once, before the loop
     if builtin_cstr is not None:
@@ -133,7 +137,12 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
                 fua = fu.reshape(M, N, xdim, udim).transpose(-1, -2).contiguous()
         # linearised costs (scp_mpc.py:171-185, 352): this iteration's references; X_ref / U_ref stay as they are for the `obj` column
         X_ref_, U_ref_ = p.X_ref, p.U_ref
-        if builtin_cost is not None:
+        if custom_cost:
+            cx, cu = s.custom_cost_grad(cost_handle[0].id, X_prev, U_prev, cost_handle[1][0])
+            X_ref_ = s.ref_shift(p.Qa, cx, X_ref_, check=False)
+            if cu is not None:
+                U_ref_ = s.ref_shift(p.Ra, cu, U_ref_, check=False)
+        elif builtin_cost is not None:
             X_ref_ = s.obstacle_cost_grad(X_prev, cost_handle, Q=p.Qa, X_ref=X_ref_, check=False)
         if lin_cost_fn is not None:
             problems = dict(ignored, f=f, fx=fxa, fu=fua, x0=p.x0, X_prev=X_prev, U_prev=U_prev, Q=p.Q, R=p.R, X_ref=p.X_ref, U_ref=p.U_ref,
@@ -142,7 +151,7 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
             if cx is not None:
                 X_ref_ = s.ref_shift(p.Qa, T(cx).reshape(M, N, xdim).contiguous(), X_ref_, check=False)
             if cu is not None:
-                U_ref_ = s.ref_shift(p.Ra, T(cu).reshape(M, N, udim).contiguous(), p.U_ref, check=False)
+                U_ref_ = s.ref_shift(p.Ra, T(cu).reshape(M, N, udim).contiguous(), U_ref_, check=False)
         t_aff = time.time()
         kw = dict(static_kw, f=f, fx=fxa, fu=fua, X_prev=X_prev, U_prev=U_prev, X_ref=X_ref_, U_ref=U_ref_,
                   static_cons_bounds=it > 0,  # the boxes are the same in every iteration of this loop (scp_mpc.py:338-376)
