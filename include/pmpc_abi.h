@@ -181,7 +181,7 @@ typedef struct pmpc_problem {
 } pmpc_problem;
 
 typedef struct pmpc_info {
-  int status;          /* 0 ok, 1 not converged (outputs NaN), 2 numerical failure (outputs NaN) */
+  int status;          /* 0 ok, 1 not converged (outputs NaN), 2 numerical failure (outputs NaN), 3 pmpc_lsoc_solve_device: infeasible start (outputs NaN) */
   int ipm_iters;       /* 0 = the equality-only optimum was feasible */
   int structured_solves; /* Riccati factorisations performed */
   int fast_path;       /* 1 = MFMA register-resident kernels were used; 2 = those kernels on fp32-stored matrices (PMPC_F32_MATRICES) */
@@ -251,8 +251,10 @@ int pmpc_lcone_solve_device(pmpc_ctx *ctx, const pmpc_problem *prob, double smoo
 
 /* The QP of pmpc_lqp_solve_device plus the stage-wise control cones of pmpc_problem.soc_* (control boxes allowed, state
  * boxes / weights / slew not): feasible primal-dual path following with Nesterov-Todd scaling on the same Riccati
- * kernels, complementarity driven to 1e-12.  Returns status (0 ok, 1 not converged, 2 numerical failure, 3 infeasible
- * start: soc_u_interior is not strictly inside the boxes and the cone). */
+ * kernels, complementarity driven to 1e-12 and — where this iteration alone answers — five centring steps at that value (an
+ * off-centre cone pair leaves the controls ~sqrt(mu) off, not ~mu).  Returns status (0 ok, 1 not converged, 2 numerical failure,
+ * 3 infeasible start: soc_u_interior is not strictly inside the boxes and the cone — a point ON a box side or on the cone counts
+ * as outside; X_out / U_out are filled with NaN as after every failed solve, and the context stays usable). */
 int pmpc_lsoc_solve_device(pmpc_ctx *ctx, const pmpc_problem *prob, pmpc_info *info, int verbose);
 
 /* J_out[i] (device, M) = J_i(X, U): per-particle cost of qp_utils.jl:60-162 (1/2 z'Pz + q'z + r), unweighted. */

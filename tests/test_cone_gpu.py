@@ -175,8 +175,10 @@ SOC_CASES = [(3, 6, 12, 4, 1, 0.8), (4, 8, 4, 2, 0, 0.6), (5, 6, 3, 3, -1, 0.6),
 
 @pytest.mark.parametrize("case", SOC_CASES, ids=[str(c) for c in SOC_CASES])
 def test_stage_cones_match_cone_oracle(case, oracle):
-    """Config E's constraint type (stage-wise second-order cones on the controls, next to the boxes) — the device's
-    primal log-barrier Newton on the Riccati kernels against the oracle's path following on the sparse joint KKT system."""
+    """Config E's constraint type (stage-wise second-order cones on the controls, next to the boxes) — the device's active-set
+    rounds with the cones inside (kernels_cone.hip: semismooth Newton on the cones' natural map; every case here is a compiled pair with a
+    symmetric cost, udim 2..4, soc_q <= 3, so the rounds answer) against the oracle's primal log-barrier path following on the sparse joint
+    KKT system.  The device's own path-following iteration (kernels_soc.hip): tests/test_soc_path_gpu.py."""
     import torch
 
     from pmpc_amd.device import DeviceSolver
@@ -199,6 +201,7 @@ def test_stage_cones_match_cone_oracle(case, oracle):
                                 soc_w0=dev(w0), soc_v=dev(v), soc_v0=v0, soc_u_interior=dev(u_int), **bounds)
     s.sync()
     assert status == 0
+    assert s.last_info["active_set_rounds"] >= 1, s.last_info  # the rounds answered (alone, or from the path-following iterate)
     X, U = X.cpu().numpy(), U.cpu().numpy()
     slack = 0.5 * U[..., 0] + 0.05 - np.linalg.norm(U[..., 1:], axis=-1)
     assert slack.min() > -1e-9 and (slack < 1e-6).sum() > 0  # inside every cone (to round-off), and the cone is active somewhere

@@ -38,6 +38,14 @@ def test_fuzz_stage_cones():
     assert m and int(m.group(1)) == 0 and float(m.group(2)) <= 1e-6, last
 
 
+def test_fuzz_stage_cones_path_following_alone():
+    """--path: cone_as = 0 and the draw widened to what only the path-following iteration serves (udim 1 and 5 .. 8, soc_q 4, uncompiled dims,
+    undeclared symmetry, forced generic kernels); the script counts a case answered by another solver as a failure."""
+    last = _run("fuzz_soc.py", 17, 10, "--path")[-1]
+    m = re.search(r"(\d+) cases \((\d+) skipped\), (\d+) failures, worst rel err ([0-9.e+-]+)", last)
+    assert m and int(m.group(1)) >= 7 and int(m.group(3)) == 0 and float(m.group(4)) <= 1e-6, last
+
+
 def test_fuzz_warm_start_sequences():
     last = _run("fuzz_warm_as.py", 13, 60, 5)[-1]
     m = re.search(r"(\d+) sequences, (\d+) solves, (\d+) failures, worst rel err ([0-9.e+-]+)", last)

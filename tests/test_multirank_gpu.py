@@ -247,6 +247,43 @@ def test_sharded_stage_cones_match_oracle(Nc, oracle):
     assert np.linalg.norm(Xw - Xo) / np.linalg.norm(Xo) < 1e-6 and np.linalg.norm(Uw - Uo) / np.linalg.norm(Uo) < 1e-6
 
 
+_path_ref = {}
+
+
+@pytest.mark.parametrize("world", [2, 4])
+@pytest.mark.parametrize("Nc", [0, 1, -1], ids=["Nc0", "Nc1", "NcAll"])
+def test_sharded_path_following_matches_single_rank_and_oracle(Nc, world, oracle):
+    """The path-following iteration alone (cone_as = 0; kernels_soc.hip instance soc3x2 on the MFMA sweeps) on sharded particles: three
+    host-staged all-reduces per Newton step (complementarity sum and count, step length as a bit pattern, step polynomial), the failure flag,
+    and a shared control's cone and boxes counted once, on rank 0's particle 0 — whose boxes differ from every other particle's here.  The second
+    solve of each context starts from the remembered iterate.  Against one rank and the oracle at the north star's 1e-6."""
+    from tests.support import soc_path as sp
+
+    if Nc not in _path_ref:  # the problem, the oracle's optimum and the one-rank solve: once per Nc, read-only afterwards
+        M, N, x, u, q = 8, 7, 5, 3, 2
+        rng = np.random.default_rng(9100 + 2 * Nc)
+        args, kw = rand_problem(rng, M, N, x, u, 0.2 if Nc < 0 else 0.5)  # (full consensus: only particle 0's boxes act, so they are tighter)
+        if Nc != 0:  # per-particle control boxes: the consensus stages must use GLOBAL particle 0's everywhere
+            scale = 1.0 + 0.5 * rng.random((M, 1, 1))
+            kw["u_l"], kw["u_u"] = kw["u_l"] * scale, kw["u_u"] * scale
+        soc = sp.cone_data(u, q, 0.3, seed=6)
+        Xo, Uo = sp.oracle_solve(oracle, args, kw, Nc, soc)
+        _path_ref[Nc] = (args, kw, soc, Xo, Uo) + _solve_sharded(args, kw, Nc, 1, repeats=2, soc=soc, options={"cone_as": 0})
+    args, kw, soc, Xo, Uo, X1, U1, info1 = _path_ref[Nc]
+    N = Uo.shape[1]
+    sp.assert_input_conditions(Uo, kw, Nc, soc)
+    Xw, Uw, infos = _solve_sharded(args, kw, Nc, world, repeats=2, soc=soc, options={"cone_as": 0})
+    for i in info1 + infos:
+        assert i["ipm_iters"] > 0 and i["active_set_rounds"] == 0 and i["fast_path"] == 1, i
+    sp.assert_matches(X1, U1, Xo, Uo, kw, Nc, soc, label=f"leg 6 one rank Nc {Nc}")
+    sp.assert_matches(Xw, Uw, Xo, Uo, kw, Nc, soc, label=f"leg 6 world {world} Nc {Nc}")
+    sp.assert_matches(Xw, Uw, X1, U1, kw, Nc, soc, label=f"leg 6 world {world} Nc {Nc} against one rank")
+    k = N if Nc < 0 else Nc
+    if k:
+        assert np.all(Uw[:, :k] == Uw[0:1, :k])  # the shared controls are bit-identical on every rank
+    assert len({(i["ipm_iters"], i["structured_solves"]) for i in infos}) == 1  # every rank took the same decisions
+
+
 _RCCL_SINGLE_SCRIPT = r"""
 import ctypes, os, sys
 import numpy as np, torch
