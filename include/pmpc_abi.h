@@ -513,13 +513,19 @@ int pmpc_custom_cost_grad_device(pmpc_ctx *ctx, int id, size_t N, size_t M, cons
  * i.e. the row a_x'x <= h with a_x[pos_idx] = -n, h = -r - n'c; every point of it is outside the ball (Cauchy-Schwarz).
  * centres (device): centre k of (particle i, stage j) is at centres + i centre_stride_particle + j centre_stride_stage + k pos_dim
  * (strides in doubles, >= 0: (0, 0) static obstacles (K, pos_dim); (0, K pos_dim) moving ones (N, K, pos_dim); (N K pos_dim, K pos_dim)
- * per particle and stage (M, N, K, pos_dim)); radius (device): (K). */
+ * per particle and stage (M, N, K, pos_dim)); radius (device): (K).
+ *
+ * kind 2, custom: a runtime-compiled state constraint loaded on the context (pmpc_cstr_load below) — `K` its row count as it was
+ * compiled, `id` its id, `gparams` (device) its parameters (M, pdim).  id and gparams share the storage of pos_dim and centres, which
+ * kind 2 does not use: the struct keeps its size and the offsets of kind 1.  pmpc_keepout_augment_device answers kind 2 with 2. */
 typedef struct pmpc_scp_cstr {
-  int kind; /* 0 none, 1 keep-out */
-  int K, pos_dim;
+  int kind; /* 0 none, 1 keep-out, 2 custom */
+  int K;
+  union { int pos_dim; int id; };
   int pos_idx[3];
   long long centre_stride_particle, centre_stride_stage;
-  const double *centres, *radius;
+  union { const double *centres; const double *gparams; };
+  const double *radius;
 } pmpc_scp_cstr;
 size_t pmpc_abi_scp_cstr_size(void); /* sizeof(pmpc_scp_cstr) as the library was built (see pmpc_abi_struct_sizes) */
 
@@ -571,6 +577,44 @@ size_t pmpc_abi_scp_aug_size(void); /* sizeof(pmpc_scp_aug) as the library was b
 int pmpc_scp_loop_device_cstr(pmpc_ctx *ctx, int model, const double *params, const pmpc_problem *p, double *f2, double *fx2,
                               double *fu2, int steps, int first_cold, double *res, pmpc_info *infos, int *last_in_out,
                               const pmpc_scp_cost *cost, const pmpc_scp_cstr *cstr, const pmpc_scp_aug *aug);
+/* Custom state constraints: g_k(X[i,j]; p_i, j, N) <= 0, k < kdim, on every stage j = 0 .. N-1 (0-based: the state after j + 1 steps, row
+ * j of X_prev) of every particle i, handed over as device code and compiled at run time like a custom model or cost.  `source` is one
+ * function template,
+ *   template <class T> __device__ void stage_cstr(const T *x, const double *p, int j, int N, T *g);
+ * x[XD] = the state, p[PD] = this particle's parameters (global memory), g[KD] = the values it writes, with XD, KD, PD defined as macros
+ * in front of it; T is double or a dual number with the operator and function set of the custom models.  Limits: XD >= 1, KD in 1 .. 4,
+ * XD + KD <= 16, PD in 1 .. 64.  About xbar = X_prev[i, j] the SCP loop imposes the rows a_k'x <= h_k, a_k = grad g_k(xbar),
+ * h_k = a_k'xbar - g_k(xbar), the gradients by forward-mode dual numbers.
+ *   pmpc_cstr_compile   as pmpc_cost_compile (no context, no GPU): 0 / 1 bad argument / 2 no runtime compiler / 3 compile error;
+ *                       pmpc_model_free_code frees *code.
+ *   pmpc_cstr_load      returns the constraint's id >= PMPC_CSTR_CUSTOM0, or -1 / -2 / -3 as pmpc_model_load.  Constraints have a table
+ *                       of their own, apart from the models' and the costs'; an id is known to the context that loaded it, until
+ *                       pmpc_cstr_unload (0; 2: not a constraint id of this context) or pmpc_destroy.
+ *   pmpc_custom_cstr_rows_device   a (M, N, K, xdim), h (M, N, K), g (M, N, K) values or NULL, at X_prev (M, N, xdim), gparams (M, pdim):
+ *                       one launch, asynchronous on pmpc_stream().  A row whose g_k or gradient holds a non-finite entry gets
+ *                       h = +inf and a = 0 (no constraint; never a NaN, the "no state bounds" sentinel of an upper bound) and counts in
+ *                       pmpc_cstr_bad_rows.  0; 1 HIP error; 2 and nothing launched: id not of this context, a null pointer (g may be
+ *                       NULL), N == 0, M == 0.
+ *   pmpc_rows_augment_device   pmpc_keepout_augment_device for K dense rows a (M, N, K, xdim), h (M, N, K) per unit instead of the ball
+ *                       geometry: the same outputs in the same layouts (xu_aug: entries xdim + k <- h_k, the first xdim NOT written).
+ *                       0; 1 HIP error; 2 and nothing launched: K outside 1 .. 4, xdim + K > 16, udim outside 1 .. 16, N == 0, M == 0,
+ *                       a null pointer (X_ref may be NULL, and X_ref_aug with it).
+ *   pmpc_cstr_bad_rows  rows refused since the context was created or the count was last reset (synchronises the stream).
+ * In pmpc_scp_loop_device_cstr a kind-2 pmpc_scp_cstr enqueues behind every linearisation launch and its shift the rows kernel into a
+ * workspace scratch and pmpc_rows_augment_device's launch into set `cur` of `aug`; everything else is the keep-out loop's.  Refused
+ * before anything runs (0, infos[0].status = 2): what kind 1 is refused with, an id that is not this context's, a constraint whose xdim
+ * or K is not the problem's / the descriptor's, null gparams. */
+#define PMPC_CSTR_CUSTOM0 1000
+int pmpc_cstr_compile(const char *source, int xdim, int kdim, int pdim, const char *arch, void **code, size_t *bytes, char *log, size_t log_cap);
+int pmpc_cstr_load(pmpc_ctx *ctx, const void *code, size_t bytes, int xdim, int kdim, int pdim);
+int pmpc_cstr_unload(pmpc_ctx *ctx, int id);
+int pmpc_custom_cstr_rows_device(pmpc_ctx *ctx, int id, size_t N, size_t M, const double *X_prev, const double *gparams, double *a, double *h,
+                                 double *g);
+int pmpc_rows_augment_device(pmpc_ctx *ctx, int K, size_t xdim, size_t udim, size_t N, size_t M, const double *a, const double *h,
+                             const double *X_prev, const double *f, const double *fx, const double *fu, const double *X_ref, double *f_aug,
+                             double *fx_aug, double *fu_aug, double *X_prev_aug, double *X_ref_aug, double *xu_aug);
+long long pmpc_cstr_bad_rows(pmpc_ctx *ctx, int reset);
+
 /* Iterations of pmpc_scp_loop_device* in this process whose follow-up (residual, next linearisation) was taken as enqueued behind the
  * sub-problem's first batch of rounds (out2[0]) / was enqueued after the solve had returned (out2[1]); reset: start counting afresh. */
 void pmpc_scp_loop_follow_ups(unsigned long long *out2, int reset);

@@ -11,8 +11,10 @@ from .backend import is_precompiled_backend_available, lcone_solve, lqp_solve  #
 from .problem_struct import Problem  # noqa: F401
 from .problem_matrices import lqp_generate_problem_matrices  # noqa: F401
 from .extra_cstrs import keepout_augment, keepout_rows, make_keepout_extra_cstrs_fn  # noqa: F401
+from .extra_cstrs import linearized_rows, make_rows_extra_cstrs_fn, rows_augment  # noqa: F401
 from .custom_model import CustomModel  # noqa: F401
 from .custom_cost import CustomCost  # noqa: F401
+from .custom_constraint import CustomConstraint  # noqa: F401
 
 
 def scp_solve_device(*args, **kw):

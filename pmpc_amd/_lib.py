@@ -36,9 +36,11 @@ ABI_SYMBOLS = [
     "pmpc_shift_active_set_device", "pmpc_warm_shift_device", "pmpc_warm_set_read_device",
     "pmpc_model_compile", "pmpc_model_free_code", "pmpc_model_load", "pmpc_model_unload",
     "pmpc_cost_compile", "pmpc_cost_load", "pmpc_cost_unload", "pmpc_custom_cost_grad_device",
+    "pmpc_cstr_compile", "pmpc_cstr_load", "pmpc_cstr_unload", "pmpc_custom_cstr_rows_device", "pmpc_rows_augment_device", "pmpc_cstr_bad_rows",
 ]
 MODEL_CUSTOM0 = 1000  # PMPC_MODEL_CUSTOM0 (include/pmpc_abi.h): ids from here on are runtime-compiled models loaded on a context
 COST_CUSTOM0 = 1000  # PMPC_COST_CUSTOM0: ids of runtime-compiled stage costs (a table of their own)
+CSTR_CUSTOM0 = 1000  # PMPC_CSTR_CUSTOM0: ids of runtime-compiled state constraints (likewise)
 
 
 class PmpcProblem(ctypes.Structure):
@@ -80,11 +82,21 @@ class PmpcScpCost(ctypes.Structure):
                 ("_c", _CentresOrCparams), ("sigma", ctypes.c_void_p), ("w", ctypes.c_void_p)]
 
 
+class _PosDimOrCstrId(ctypes.Union):
+    _fields_ = [("pos_dim", ctypes.c_int), ("id", ctypes.c_int)]
+
+
+class _CentresOrGparams(ctypes.Union):
+    _fields_ = [("centres", ctypes.c_void_p), ("gparams", ctypes.c_void_p)]
+
+
 class PmpcScpCstr(ctypes.Structure):
-    """pmpc_scp_cstr (include/pmpc_abi.h): the built-in constraint of pmpc_keepout_augment_device."""
-    _fields_ = [("kind", ctypes.c_int), ("K", ctypes.c_int), ("pos_dim", ctypes.c_int), ("pos_idx", ctypes.c_int * 3),
+    """pmpc_scp_cstr (include/pmpc_abi.h): the constraint of pmpc_scp_loop_device_cstr — kind 1 the built-in keep-out, kind 2 a loaded
+    custom constraint, whose id / gparams share the storage of pos_dim / centres (K is the row count of both)."""
+    _anonymous_ = ("_a", "_b")
+    _fields_ = [("kind", ctypes.c_int), ("K", ctypes.c_int), ("_a", _PosDimOrCstrId), ("pos_idx", ctypes.c_int * 3),
                 ("centre_stride_particle", ctypes.c_longlong), ("centre_stride_stage", ctypes.c_longlong),
-                ("centres", ctypes.c_void_p), ("radius", ctypes.c_void_p)]
+                ("_b", _CentresOrGparams), ("radius", ctypes.c_void_p)]
 
 
 class PmpcScpAug(ctypes.Structure):
@@ -249,6 +261,19 @@ def load():
         lib.pmpc_cost_unload.restype = ctypes.c_int
         lib.pmpc_custom_cost_grad_device.argtypes = [vp, ctypes.c_int, sz, sz] + [vp] * 6
         lib.pmpc_custom_cost_grad_device.restype = ctypes.c_int
+    if hasattr(lib, "pmpc_cstr_compile"):  # (likewise: runtime-compiled state constraints)
+        lib.pmpc_cstr_compile.argtypes = [ctypes.c_char_p] + [ctypes.c_int] * 3 + [ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.c_char_p, sz]
+        lib.pmpc_cstr_compile.restype = ctypes.c_int
+        lib.pmpc_cstr_load.argtypes = [vp, ctypes.c_char_p, sz] + [ctypes.c_int] * 3
+        lib.pmpc_cstr_load.restype = ctypes.c_int
+        lib.pmpc_cstr_unload.argtypes = [vp, ctypes.c_int]
+        lib.pmpc_cstr_unload.restype = ctypes.c_int
+        lib.pmpc_custom_cstr_rows_device.argtypes = [vp, ctypes.c_int, sz, sz] + [vp] * 5
+        lib.pmpc_custom_cstr_rows_device.restype = ctypes.c_int
+        lib.pmpc_rows_augment_device.argtypes = [vp, ctypes.c_int, sz, sz, sz, sz] + [vp] * 13
+        lib.pmpc_rows_augment_device.restype = ctypes.c_int
+        lib.pmpc_cstr_bad_rows.argtypes = [vp, ctypes.c_int]
+        lib.pmpc_cstr_bad_rows.restype = ctypes.c_longlong
     lib.pmpc_version.argtypes = []
     lib.pmpc_version.restype = ctypes.c_char_p
     # layout check: the library's structs against this binding's mirrors (include/pmpc_abi.h: pmpc_abi_struct_sizes)

@@ -76,6 +76,7 @@ struct Workspace {
   DevBuf jac_tmp;  // compact Jacobian records copied aside while they are expanded into the caller's fx / fu (QpSolve::densify)
   DevBuf cost_ref[2];  // pmpc_scp_loop_device_cost: the shifted reference X_ref - Q^-1 cx, one per linearisation scratch set
   DevBuf cost_uref[2], cost_grad;  // a kind-2 cost: U_ref - R^-1 cu, sets as cost_ref; the gradient scratch (cx | cu), one set
+  DevBuf cstr_rows, cstr_bad;  // a kind-2 constraint: the rows scratch (a | h), one set; rows pmpc_jit_cstr_rows refused (one unsigned counter)
   DevBuf cost_bad;  // blocks pmpc_ref_shift_device refused (one unsigned counter; cost_lin.hip)
   DevBuf m64[4];  // fp32-storage mode: fx, fu, Q, R widened for the paths that run the fp64 kernels
   // warm start: the early interior-point iterate (mu <= 0.5) remembered from the previous solve of the same shape

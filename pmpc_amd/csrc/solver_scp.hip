@@ -7,6 +7,8 @@
 #include "keepout.h"
 #include "model_jit.h"
 #include "cost_jit.h"
+#include "cstr_jit.h"
+#include "cstr_rows.h"
 
 static std::atomic<unsigned long long> g_follow_ups[2];  // iterations whose follow-up was taken as enqueued behind the rounds / enqueued after the solve
 
@@ -50,6 +52,10 @@ struct ScpLoop {
   // iterate-dependent ones have two sets, indexed like F; the augmentation goes behind every linearisation launch and its shift.  The
   // trajectory pairs stay at x: the sub-problem's states land in aug->X_out and the follow-up strips them into the pair.
   const bool with_cstr;
+  // Custom constraint (kind 2, cstr_jit.hip): behind every linearisation launch and its shift the rows kernel writes (a | h) about the
+  // iterate into one workspace scratch and k_rows_augment (cstr_rows.hip) turns them into set `set` of the augmented buffers, where the
+  // keep-out kernel does both at once; the sub-problem and the follow-up are the keep-out loop's.
+  const bool custom_cstr;
   const int K;
   const bool soc;
   const bool cone_obj;  // the sub-problem is the reference's default path (c_lcone_solve)
@@ -65,7 +71,8 @@ struct ScpLoop {
 
   // ---- state of the iteration ----
   double *Xr[2] = {nullptr, nullptr}, *Ur[2] = {nullptr, nullptr}, *cgrad = nullptr;
-  unsigned *cost_bad = nullptr;
+  unsigned *cost_bad = nullptr, *cstr_bad = nullptr;
+  double *crows = nullptr;  // a kind-2 constraint's rows about the iterate: a (M, N, K, x) | h (M, N, K)
   bool compact_set[2] = {false, false};  // what the linearisation buffer sets hold
   int done = 0, cur = 0;
   double *Xp = nullptr, *Up = nullptr, *Xo = nullptr, *Uo = nullptr;  // this iteration's (X_prev, U_prev) and (X_out, U_out) of the pairs
@@ -76,7 +83,7 @@ struct ScpLoop {
       : c(c_), model(model_), params(params_), p0(p), steps(steps_), first_cold(first_cold_), res(res_), infos(infos_), cost(cost_), cstr(cstr_),
         aug(aug_), x((int)p->xdim), u((int)p->udim), N((int)p->N), M((int)p->M), with_cost(cost_ != nullptr && cost_->kind != 0),
         custom_cost(with_cost && cost_->kind == 2), cost_u(custom_cost && cost_->uses_u != 0),
-        with_cstr(cstr_ != nullptr && cstr_->kind != 0), K(with_cstr ? cstr_->K : 0), soc(p->soc_u_interior != nullptr || p->cone_count > 0),
+        with_cstr(cstr_ != nullptr && cstr_->kind != 0), custom_cstr(with_cstr && cstr_->kind == 2), K(with_cstr ? cstr_->K : 0), soc(p->soc_u_interior != nullptr || p->cone_count > 0),
         cone_obj((p->flags & PMPC_CONE_OBJECTIVE) != 0), jac32((p->flags & PMPC_F32_MATRICES) ? 1 : 0),
         compact_ok(lin_compact_env() && !with_cstr && !cone_obj && !jac32 && !c_->multi() && p->Nc >= 0 && p->Nc <= 1 && jac_compact_dims(model_, x, u) &&
                    (p->flags & PMPC_SYMMETRIC_COST) && !(p->flags & (PMPC_HAS_SLEW | PMPC_HAS_SLEW0 | PMPC_FORCE_GENERIC | PMPC_COLD_START)) &&
@@ -107,7 +114,12 @@ struct ScpLoop {
     }
     // (a constraint description the kernels cannot run, incomplete augmented buffers, and a constraint next to what rows on the states are
     //  not solved with: a stage cone, slew penalties, fp32-stored matrices, a sharded context, the squareplus smoothing of the boxes)
-    return with_cstr && (!keepout_cstr_valid(cstr, x) || !keepout_strip_dims_valid(p0->xdim, K, p0->udim) || !scp_aug_complete(aug) || soc ||
+    // (a custom constraint that is not this context's, whose dimensions are not the problem's and the descriptor's, or without parameters)
+    if (custom_cstr) {
+      int gx = 0, gk = 0;
+      if (!custom_cstr_known(c, cstr->id) || !custom_cstr_dims(cstr->id, &gx, &gk, nullptr) || gx != x || gk != K || !cstr->gparams) return true;
+    }
+    return with_cstr && ((!custom_cstr && !keepout_cstr_valid(cstr, x)) || !keepout_strip_dims_valid(p0->xdim, K, p0->udim) || !scp_aug_complete(aug) || soc ||
                          (p0->flags & (PMPC_HAS_SLEW | PMPC_HAS_SLEW0)) || jac32 || c->multi() || p0->smooth_cstr == 1);
   }
 
@@ -137,8 +149,14 @@ struct ScpLoop {
     } else if (with_cost) {
       launch_obstacle_ref_shift(*cost, x, N, M, X, p0->Q, p0->X_ref, Xr[set], cost_bad, c->stream);
     }
-    if (with_cstr)  // (the reference it extends: this iteration's shifted one, else the caller's)
-      launch_keepout_augment(*cstr, x, u, N, M, X, f[0], f[1], f[2], with_cost ? Xr[set] : p0->X_ref, aug->f[set], aug->fx[set], aug->fu[set],
+    const double *ref = with_cost ? Xr[set] : p0->X_ref;  // (the reference a constraint extends: this iteration's shifted one, else the caller's)
+    if (custom_cstr) {
+      double *h = crows + (long long)M * N * K * x;
+      custom_launch_cstr_rows(cstr->id, N, M, X, cstr->gparams, crows, h, nullptr, cstr_bad, c->stream);
+      launch_rows_augment(K, x, u, N, M, crows, h, X, f[0], f[1], f[2], ref, aug->f[set], aug->fx[set], aug->fu[set], aug->X_prev[set], aug->X_ref[set],
+                          aug->xu[set], c->stream);
+    } else if (with_cstr)
+      launch_keepout_augment(*cstr, x, u, N, M, X, f[0], f[1], f[2], ref, aug->f[set], aug->fx[set], aug->fu[set],
                              aug->X_prev[set], aug->X_ref[set], aug->xu[set], c->stream);
   }
 
@@ -207,6 +225,11 @@ struct ScpLoop {
         for (DevBuf &b : c->ws.cost_uref) b.ensure(rows * p0->udim * sizeof(double));
         Ur[0] = c->ws.cost_uref[0].d(); Ur[1] = c->ws.cost_uref[1].d();
       }
+    }
+    if (custom_cstr) {
+      c->ws.cstr_rows.ensure((size_t)p0->M * p0->N * K * (p0->xdim + 1) * sizeof(double));
+      crows = c->ws.cstr_rows.d();
+      cstr_bad = cstr_bad_counter(c);
     }
     bool lin_ready = false;  // the linearisation of iteration `done` is already enqueued (valid speculation of the previous one)
     for (; done < steps; done++, cur ^= 1) {

@@ -51,6 +51,7 @@ class DeviceSolver:
         self.last_info: Dict[str, float] = {}
         self._custom: Dict[int, object] = {}  # model id -> the CustomModel loaded under it (load_model)
         self._costs: Dict[int, object] = {}  # cost id -> the CustomCost loaded under it (load_cost); a table apart from the models'
+        self._cstrs: Dict[int, object] = {}  # constraint id -> the CustomConstraint loaded under it (load_cstr); likewise
 
     # ---- runtime-compiled dynamics models (pmpc_amd/custom_model.py) -----------------------------------
     def load_model(self, cm) -> int:
@@ -135,6 +136,86 @@ class DeviceSolver:
             raise RuntimeError(f"pmpc_custom_cost_grad_device failed ({st})")
         return (cx, cu, val) if val is not None else (cx, cu)
 
+    # ---- runtime-compiled state constraints (pmpc_amd/custom_constraint.py) ---------------------------
+    def load_cstr(self, cc) -> int:
+        """The constraint id (>= 1000, in a table of its own) of a `pmpc_amd.CustomConstraint` on this solver: compiled for the device's
+        architecture and loaded on first use, the same id from then on.  It is known to this solver only and goes with `unload_cstr` or
+        `close`."""
+        self._need("pmpc_cstr_load")
+        for gid, loaded in self._cstrs.items():
+            if loaded is cc:
+                return gid
+        arch = torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0]  # the target id alone, never a feature suffix
+        code = cc.compile(arch)
+        gid = self.lib.pmpc_cstr_load(self.h, code, len(code), cc.xdim, cc.kdim, cc.pdim)
+        if gid < _lib.CSTR_CUSTOM0:
+            raise RuntimeError(f"pmpc_cstr_load failed ({gid}) for {cc!r}")
+        self._cstrs[gid] = cc
+        return gid
+
+    def unload_cstr(self, cstr: int) -> None:
+        self._cstrs.pop(int(cstr), None)
+        if self.lib.pmpc_cstr_unload(self.h, int(cstr)) != 0:
+            raise ValueError(f"constraint {cstr} is not a custom constraint loaded on this solver")
+
+    def check_bad_rows(self, what):
+        """Raise ValueError if the rows kernel of a custom constraint since the last check met a row whose value or gradient is not finite
+        (reads and clears the device-side counter; synchronises the solver's stream)."""
+        self._need("pmpc_cstr_bad_rows")
+        n = self.lib.pmpc_cstr_bad_rows(self.h, 1)
+        if n:
+            raise ValueError(f"{what}: {n} constraint row(s) had a non-finite value or gradient at the iterate (they were dropped: h = +inf, a = 0)")
+
+    def custom_cstr_rows(self, cstr, X_prev, gparams, value=False, a=None, h=None, wait_current_stream=True, check=False):
+        """(a (M, N, K, x), h (M, N, K)) — with `value` also g (M, N, K), the constraint's values — of a custom constraint about X_prev with
+        the parameters gparams (M, pdim): the rows a_k'x <= h_k, one launch of the kernel compiled from the user's `stage_cstr`.  `cstr`: a
+        `pmpc_amd.CustomConstraint` (loaded on first use) or the id of `load_cstr`.  `a` / `h`, and a tensor given as `value`: preallocated
+        outputs.  A row with a non-finite value or gradient comes back as h = +inf, a = 0 and counts for `check_bad_rows` (`check`: read it now)."""
+        self._need("pmpc_custom_cstr_rows_device")
+        gid = self.load_cstr(cstr) if not isinstance(cstr, int) else int(cstr)
+        cc = self._cstrs.get(gid)
+        if cc is None:
+            raise ValueError(f"constraint {gid} is not a custom constraint loaded on this solver")
+        M, N, x = X_prev.shape
+        cc.check_problem(M, x, gparams)
+        K, dev = cc.kdim, X_prev.device
+        a = torch.empty((M, N, K, x), dtype=torch.float64, device=dev) if a is None else a
+        h = torch.empty((M, N, K), dtype=torch.float64, device=dev) if h is None else h
+        g = value if torch.is_tensor(value) else (torch.empty((M, N, K), dtype=torch.float64, device=dev) if value else None)
+        assert a.shape == (M, N, K, x) and h.shape == (M, N, K) and (g is None or g.shape == (M, N, K))
+        self._before(wait_current_stream)
+        st = self.lib.pmpc_custom_cstr_rows_device(self.h, gid, N, M, _p(X_prev), _p(gparams), _p(a), _p(h), _p(g))
+        self._after(wait_current_stream)
+        if st != 0:
+            raise RuntimeError(f"pmpc_custom_cstr_rows_device failed ({st})")
+        if check:
+            self.check_bad_rows("custom_cstr_rows")
+        return (a, h, g) if g is not None else (a, h)
+
+    def rows_augment(self, a, h, X_prev, f, fx, fu, X_ref=None, out=None, wait_current_stream=True):
+        """`keepout_augment` for K dense rows a (M, N, K, x), h (M, N, K) per (particle, stage) instead of the ball geometry
+        (pmpc_amd.extra_cstrs.rows_augment is the specification), one launch: the same dict in the same layouts."""
+        self._need("pmpc_rows_augment_device")
+        M, N, x = X_prev.shape
+        u, K = fu.shape[-2], h.shape[-1]
+        xd = x + K
+        assert a.shape == (M, N, K, x) and h.shape == (M, N, K), (a.shape, h.shape)
+        assert f.shape == (M, N, x) and fx.shape == (M, N, x, x) and fu.shape == (M, N, u, x) and (X_ref is None or X_ref.shape == (M, N, x))
+        if not 1 <= K <= 4 or xd > 16:
+            raise ValueError(f"rows_augment: {K} rows on {x} states are outside 1 .. 4 rows, 16 states in all")
+        if out is None:
+            mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=X_prev.device)
+            out = dict(f=mk(M, N, xd), fx=mk(M, N, xd, xd), fu=mk(M, N, u, xd), X_prev=mk(M, N, xd), X_ref=mk(M, N, xd), xu=mk(M, N, xd))
+        for k, shape in (("f", (M, N, xd)), ("fx", (M, N, xd, xd)), ("fu", (M, N, u, xd)), ("X_prev", (M, N, xd)), ("X_ref", (M, N, xd)), ("xu", (M, N, xd))):
+            assert out[k].shape == shape, (k, out[k].shape, shape)
+        self._before(wait_current_stream)
+        st = self.lib.pmpc_rows_augment_device(self.h, K, x, u, N, M, _p(a), _p(h), _p(X_prev), _p(f), _p(fx), _p(fu), _p(X_ref), _p(out["f"]),
+                                               _p(out["fx"]), _p(out["fu"]), _p(out["X_prev"]), _p(out["X_ref"]), _p(out["xu"]))
+        self._after(wait_current_stream)
+        if st != 0:
+            raise RuntimeError(f"pmpc_rows_augment_device failed ({st})")
+        return out
+
     def set_option(self, key: str, value: float) -> None:
         """Per-context algorithm switch (include/pmpc_abi.h, pmpc_set_option): e.g. ``set_option("xbox_as", 0)``."""
         if self.lib.pmpc_set_option(self.h, key.encode(), float(value)) != 0:
@@ -150,7 +231,7 @@ class DeviceSolver:
         if getattr(self, "h", None):
             self.lib.pmpc_destroy(self.h)  # (unloads the custom models with everything else)
             self.h = None
-            self._custom, self._costs = {}, {}
+            self._custom, self._costs, self._cstrs = {}, {}, {}
 
     def __del__(self):
         try:
@@ -532,10 +613,24 @@ class DeviceSolver:
     def prepare_cstr(self, cstr, M, N, x, device="cuda"):
         """A handle of a built-in constraint dict(kind="keepout", pos_idx=, centres=, radius=) for repeated `keepout_augment` calls on
         (M particles, N stages, x states): the descriptor and its device arrays, uploaded once.  centres: (K, pos_dim) static,
-        (N, K, pos_dim) per stage, (M, N, K, pos_dim) per particle and stage.  A handle passes through."""
+        (N, K, pos_dim) per stage, (M, N, K, pos_dim) per particle and stage.  A handle passes through.
+        dict(kind="custom", cstr=pmpc_amd.CustomConstraint, params=(M, pdim)): the constraint is loaded on this solver and params uploaded; a
+        kind-2 descriptor whose second entry is [params on the device, the CustomConstraint] (`scp_loop` takes it; `keepout_augment` does not)."""
         self._need("pmpc_keepout_augment_device")
         if isinstance(cstr, tuple):
             return cstr
+        from .custom_constraint import check_cstr_dict, is_custom
+
+        if is_custom(cstr):
+            self._need("pmpc_cstr_load")
+            check_cstr_dict(cstr, M, x)  # (host side, before anything is loaded)
+            cc = cstr["cstr"]
+            gid = self.load_cstr(cc)
+            gparams = torch.as_tensor(cstr["params"], dtype=torch.float64).to(device).reshape(M, cc.pdim).contiguous()
+            if torch.is_tensor(cstr["params"]) and gparams.data_ptr() == cstr["params"].data_ptr():
+                gparams = gparams.clone()  # (the handle's array is its own: MPCController.set_constraint_params writes it in place)
+            torch.cuda.current_stream(self.device).synchronize()  # (uploaded on the caller's stream; the kernels read it on the solver's)
+            return _lib.PmpcScpCstr(kind=2, K=cc.kdim, id=gid, gparams=gparams.data_ptr()), [gparams, cc]
         from .extra_cstrs import _keepout_arrays
 
         pos_idx, cen, rad = _keepout_arrays(cstr, M, N, x, _TorchF64(device))
@@ -558,6 +653,8 @@ class DeviceSolver:
         M, N, x = X_prev.shape
         u = fu.shape[-2]
         sc, keep = self.prepare_cstr(cstr, M, N, x, X_prev.device)
+        if sc.kind != 1:
+            raise ValueError("keepout_augment takes the keep-out constraint; a custom constraint goes through custom_cstr_rows and rows_augment")
         xd = x + sc.K
         assert f.shape == (M, N, x) and fx.shape == (M, N, x, x) and fu.shape == (M, N, u, x) and (X_ref is None or X_ref.shape == (M, N, x))
         if out is None:
@@ -615,7 +712,8 @@ class DeviceSolver:
         with symmetric positive definite blocks; refused with status 2 next to float32 matrices).  `cost=dict(kind="custom",
         cost=pmpc_amd.CustomCost, params=(M, pdim))`: the user's stage cost (`custom_cost_grad`); the sub-problem tracks X_ref - Q^-1 cx
         and, unless the cost has uses_u=False, U_ref - R^-1 cu (R likewise).
-        `cstr=`: a keep-out constraint, the dict of `prepare_cstr` or its handle, with `aug=pmpc_amd.device_problem.keepout_buffers(problem, K)`
+        `cstr=`: a keep-out constraint or dict(kind="custom", cstr=pmpc_amd.CustomConstraint, params=(M, pdim)) (rows about every iterate from
+        `custom_cstr_rows`, augmented by `rows_augment`; K = kdim), the dict of `prepare_cstr` or its handle, with `aug=pmpc_amd.device_problem.keepout_buffers(problem, K)`
         (two sets), allocated once by the caller: every iteration's sub-problem runs at x + K states on those buffers (`keepout_augment`'s
         launch in front of it, `strip_residual`'s behind it); everything this method takes and returns stays at x states.  Refused by
         the library with status 2: a stage cone, slew penalties, float32 matrices, a sharded context, smooth_cstr="squareplus"."""
@@ -661,6 +759,8 @@ class DeviceSolver:
         self._after(wait_current_stream)
         if cost is not None:
             self.check_bad_pivots("scp_loop(cost=...): Q" + (" or R" if sc.kind == 2 else ""))
+        if cstr is not None and cs.kind == 2:
+            self.check_bad_rows("scp_loop(cstr=...)")
         out = [{k: getattr(infos[i], k) for k, _ in _lib.PmpcInfo._fields_} for i in range(min(done + 1, steps))]
         if out:
             self.last_info = out[min(done, steps) - 1] if done > 0 else out[0]

@@ -372,7 +372,8 @@ def _keepout_arrays(cstr, M, N, xdim=None, xp=np):
     """(pos_idx list, centres broadcastable to (M, N, K, pos_dim) as a 4-d array, radius (K,)) of dict(kind="keepout", pos_idx=, centres=,
     radius=): centres (K, pos_dim) static, (N, K, pos_dim) per stage, (M, N, K, pos_dim) per particle and stage."""
     if cstr.get("kind", "keepout") != "keepout":
-        raise ValueError(f"unknown built-in constraint kind {cstr.get('kind')!r}: 'keepout' is the only one")
+        raise ValueError(f"unknown built-in constraint kind {cstr.get('kind')!r}: 'keepout' is the only one with ball geometry "
+                         '(a pmpc_amd.CustomConstraint enters as dict(kind="custom", cstr=, params=))')
     pos_idx = [int(k) for k in cstr["pos_idx"]]
     centres, radius = xp.asarray(cstr["centres"]), xp.asarray(cstr["radius"]).reshape(-1)
     K, pd = int(radius.shape[0]), len(pos_idx)
@@ -460,6 +461,79 @@ def make_keepout_extra_cstrs_fn(cstr, Nc=-1):
         cols = (ncu + unit * x)[:, None] + np.asarray(pos_idx)[None, :]
         vals = a_x.reshape(l, x)[:, pos_idx]
         G = sp.csr_matrix((vals.reshape(-1), (rows, cols.reshape(-1))), shape=(l, n))
+        return [(l, [], 0, G, sp.csr_matrix((l, 0)), h.reshape(-1).copy(), np.zeros(n), np.zeros(0))]
+
+    return extra_cstrs_fn
+
+
+# -------------------------------------------------------------------------------------------------
+# dense rows on the states (a custom constraint, pmpc_amd/custom_constraint.py; specification of csrc/cstr_rows.hip k_rows_augment)
+# -------------------------------------------------------------------------------------------------
+def rows_augment(a_x, h, x0, f, fx, fu, X_prev, X_ref, Q, reg_x, x_l=None, x_u=None):
+    """`aux_state_problem` for "K dense rows a_x[i, j, k]'X[i, j] <= h[i, j, k] (form 0) on every (particle, stage)", dense and batched (py
+    layout in and out; a_x (M, N, K, x), h (M, N, K)): the state grows to xd = x + K, component x + k of f~ is a_x'f, its row of fx~ / fu~
+    is a_x'fx / a_x'fu, the auxiliary block of Q~ is -reg_x, the auxiliary entries of X_prev~, X_ref~, x0~ are 0, their bounds (-inf, h);
+    the first x bounds are the caller's boxes (-+inf if none).  `keepout_augment` is this with `keepout_rows`'s rows.
+    Returns dict(x0, f, fx, fu, X_prev, Q, X_ref, x_l, x_u, m=K) as `aux_state_problem` does."""
+    a_x, h = np.asarray(a_x, float), np.asarray(h, float)
+    f, fx, fu = np.asarray(f, float), np.asarray(fx, float), np.asarray(fu, float)
+    M, N, x = f.shape
+    u = fu.shape[-1]
+    K = h.shape[-1]
+    assert a_x.shape == (M, N, K, x) and h.shape == (M, N, K), (a_x.shape, h.shape)
+    xd = x + K
+    F = np.zeros((M, N, xd)); F[..., :x] = f
+    F[..., x:] = np.einsum("mnkx,mnx->mnk", a_x, f)
+    FX = np.zeros((M, N, xd, xd)); FX[..., :x, :x] = fx
+    FX[..., x:, :x] = np.einsum("mnkx,mnxc->mnkc", a_x, fx)
+    FU = np.zeros((M, N, xd, u)); FU[..., :x, :] = fu
+    FU[..., x:, :] = np.einsum("mnkx,mnxc->mnkc", a_x, fu)
+    XP = np.zeros((M, N, xd)); XP[..., :x] = X_prev
+    XR = np.zeros((M, N, xd)); XR[..., :x] = X_ref
+    QQ = np.zeros((M, N, xd, xd)); QQ[..., :x, :x] = Q
+    QQ[..., np.arange(x, xd), np.arange(x, xd)] = -float(reg_x)
+    X0 = np.zeros((M, xd)); X0[:, :x] = x0
+    lo = np.full((M, N, xd), -np.inf); hi = np.full((M, N, xd), np.inf)
+    if x_l is not None and np.size(x_l):
+        lo[..., :x] = np.broadcast_to(x_l, (M, N, x))
+    if x_u is not None and np.size(x_u):
+        hi[..., :x] = np.broadcast_to(x_u, (M, N, x))
+    lo[np.isnan(lo)], hi[np.isnan(hi)] = -np.inf, np.inf
+    hi[..., x:] = h
+    return dict(x0=X0, f=F, fx=FX, fu=FU, X_prev=XP, Q=QQ, X_ref=XR, x_l=lo, x_u=hi, m=K)
+
+
+def linearized_rows(g_fn, jac_fn, X_prev):
+    """The convexification of g(x) <= 0 about X_prev (M, N, x): `(a_x (M, N, K, x), h (M, N, K))` with a_x = jac_fn(X_prev) (the Jacobian
+    dg_k / dx, (M, N, K, x)) and h = a_x'X_prev - g_fn(X_prev) (g_fn: (M, N, K); stage j is axis 1) — the row  a_x'X[i, j] <= h  is
+    g(xbar) + dg(xbar)(x - xbar) <= 0."""
+    X_prev = np.asarray(X_prev, float)
+    a_x, g = np.asarray(jac_fn(X_prev), float), np.asarray(g_fn(X_prev), float)
+    return a_x, np.einsum("mnkx,mnx->mnk", a_x, X_prev) - g
+
+
+def make_rows_extra_cstrs_fn(g_fn, jac_fn, Nc=-1):
+    """An `extra_cstrs_fns(X_prev, U_prev, problems)` callable of a state constraint g(x) <= 0 for the host loop (and for upstream pmpc):
+    one reference-format tuple `(l, [], 0, G_left, ...)` with the M N K rows of `linearized_rows(g_fn, jac_fn, X_prev)`, ordered (particle,
+    stage, row), dense over the unit's x states, over z = [U_cons; U_free; X].  `g_fn(X) -> (M, N, K)`, `jac_fn(X) -> (M, N, K, x)` for
+    X (M, N, x), stage j on axis 1.  `Nc`: the `solver_settings["Nc"]` of the solve, as for `make_keepout_extra_cstrs_fn`."""
+
+    def extra_cstrs_fn(X_prev, U_prev, problems=None):
+        X_prev = np.asarray(X_prev, float)
+        single = X_prev.ndim == 2
+        Xp = X_prev[None] if single else X_prev
+        M, N, x = Xp.shape
+        u = np.asarray(U_prev).shape[-1]
+        Ncc = N if Nc < 0 else min(int(Nc), N)
+        ncu = Ncc * u + M * (N - Ncc) * u
+        n = ncu + M * N * x
+        a_x, h = linearized_rows(g_fn, jac_fn, Xp)
+        K = h.shape[-1]
+        l = M * N * K
+        unit = np.repeat(np.arange(M * N), K)  # row r = (i N + j) K + k
+        rows = np.repeat(np.arange(l), x)
+        cols = (ncu + unit * x)[:, None] + np.arange(x)[None, :]
+        G = sp.csr_matrix((a_x.reshape(-1), (rows, cols.reshape(-1))), shape=(l, n))
         return [(l, [], 0, G, sp.csr_matrix((l, 0)), h.reshape(-1).copy(), np.zeros(n), np.zeros(0))]
 
     return extra_cstrs_fn

@@ -28,6 +28,10 @@ restates the controls as states) and `keepout=` (its loop clears the promise the
 cost, or `dict(kind="custom", cost=pmpc_amd.CustomCost, params=)`, whose parameters `set_cost_params` rewrites in place) is allowed;
 without control boxes nothing is stored and every step stays cold.
 
+`constraint=dict(cstr=pmpc_amd.CustomConstraint, params=(M, pdim))` is the user's own state constraint g(x) <= 0 carried the same way
+(`set_constraint_params` rewrites its parameters in place); refused next to `keepout=` (the loop carries one constraint) and with what
+`keepout=` is refused with, `warm_shift=True` included.  A row whose value or gradient is not finite at an iterate is a `ValueError`.
+
 `keepout=dict(pos_idx=, centres=, radius=)` is the hard keep-out constraint of `solve(..., device=..., builtin_cstr=...)` (1 to 4 balls in the
 position sub-space `pos_idx`; centres `(K, pos_dim)`, `(N, K, pos_dim)` per stage or `(M, N, K, pos_dim)` per particle and stage) carried
 through the library loop: every sub-problem runs at `xdim + K` states on augmented buffers the constructor allocates once, the plan
@@ -53,6 +57,7 @@ import torch
 
 from .device import DeviceSolver
 from .device_problem import build_problem, keepout_buffers
+from .custom_constraint import check_cstr_dict
 from .custom_cost import check_cost_dict, is_custom
 from .custom_model import CustomModel
 from .dynamics import model_id
@@ -60,7 +65,7 @@ from .dynamics import model_id
 _SETTINGS = ("solver", "Nc", "smooth_alpha", "slew_reg", "extra_cstrs", "soc_u_interior")
 
 
-def _refuse_with_warm_shift(settings, soc, x_l, x_u, slew_rate, keepout):
+def _refuse_with_warm_shift(settings, soc, x_l, x_u, slew_rate, keepout, constraint=None):
     """`warm_shift=True` moves the control-box statuses and the plan's controls and nothing else: refused next to every feature whose
     solve carries a warm-start memory of its own that stays at the old stages (or that ends the warm first iteration anyway)."""
     from .device_problem import _CONE_SOLVERS
@@ -78,6 +83,8 @@ def _refuse_with_warm_shift(settings, soc, x_l, x_u, slew_rate, keepout):
         why = "slew penalties (slew_rate, slew_reg): their increment form restates the controls as states, whose rows are not shifted"
     elif keepout is not None:
         why = "keepout=: its rows are state rows (not shifted), and the keep-out loop runs no sub-problem as a no-rollout warm start"
+    elif constraint is not None:
+        why = "constraint=: its rows are state rows (not shifted), and the constrained loop runs no sub-problem as a no-rollout warm start"
     if why is not None:
         raise ValueError(f"MPCController: warm_shift=True is not supported next to {why}")
 
@@ -86,7 +93,8 @@ class MPCController:
     def __init__(self, builtin_model=None, params=None, Q=None, R=None, X_ref=None, U_ref=None, u_l=None, u_u=None, x_l=None, x_u=None,
                  reg_x: float = 1e0, reg_u: float = 1e-2, solver_settings: Optional[Dict[str, Any]] = None, builtin_cost: Optional[Dict[str, Any]] = None,
                  slew_rate: Optional[float] = None, u0_slew=None, soc: Optional[Dict[str, Any]] = None, device="cuda",
-                 solver: Optional[DeviceSolver] = None, keepout: Optional[Dict[str, Any]] = None, warm_shift: bool = False, **unsupported):
+                 solver: Optional[DeviceSolver] = None, keepout: Optional[Dict[str, Any]] = None, warm_shift: bool = False,
+                 constraint: Optional[Dict[str, Any]] = None, **unsupported):
         if builtin_model is None:
             raise ValueError("MPCController needs builtin_model=: a Python f_fx_fu_fn cannot enter the library's SCP loop")
         if unsupported.get("builtin_cstr") is not None:
@@ -97,9 +105,12 @@ class MPCController:
             raise ValueError(f"MPCController does not support {sorted(bad)}; the host loop pmpc_amd.solve(...) has the host-only features")
         settings = dict(solver_settings or {})
         if warm_shift:  # what the shifted memory does not cover: before any device is touched
-            _refuse_with_warm_shift(settings, soc, x_l, x_u, slew_rate, keepout)
+            _refuse_with_warm_shift(settings, soc, x_l, x_u, slew_rate, keepout, constraint)
         self.warm_shift = bool(warm_shift)
-        if keepout is not None:  # what the constraint is refused with, for scp_device.py's reasons: before any device is touched
+        if constraint is not None and keepout is not None:
+            raise ValueError("MPCController: constraint= is not supported next to keepout= (the loop carries one constraint: a keep-out ball is "
+                             "g = r - |x[pos] - c| in a pmpc_amd.CustomConstraint)")
+        if keepout is not None or constraint is not None:  # what the constraint is refused with, for scp_device.py's reasons: before any device is touched
             from .scp_device import _refuse_with_cstr
 
             _refuse_with_cstr(settings, soc, slew_rate, u0_slew, solver)
@@ -117,6 +128,9 @@ class MPCController:
         if custom:  # dimensions and params that are not the model's: likewise before any device is touched
             builtin_model.check_problem(np.shape(Q)[0], np.shape(Q)[-1], np.shape(R)[-1], params)
         check_cost_dict(builtin_cost, np.shape(Q)[0], np.shape(Q)[-1], np.shape(R)[-1])  # (a custom cost: likewise)
+        if constraint is not None:  # (a custom constraint: likewise)
+            constraint = dict(constraint, kind="custom")
+            check_cstr_dict(constraint, np.shape(Q)[0], np.shape(Q)[-1])
         if keepout is not None:  # a description the kernels cannot run: likewise before any device is touched
             from .extra_cstrs import _keepout_arrays
 
@@ -160,8 +174,9 @@ class MPCController:
         # the keep-out constraint: the descriptor with its device arrays (`set_keepout` writes them in place) and the augmented buffers
         # of the library loop, both made once; x0~ = [x0 | 0] is refreshed from x0 every step
         self._cstr = self._aug = None
-        if keepout is not None:
-            self._cstr = s.prepare_cstr(keepout, M, N, x, dev)
+        self._custom_cstr = constraint is not None
+        if keepout is not None or constraint is not None:
+            self._cstr = s.prepare_cstr(keepout if keepout is not None else constraint, M, N, x, dev)
             p.x0 = self._x0
             self._aug = keepout_buffers(p, self._cstr[0].K, sets=2)
         torch.cuda.current_stream(dev).synchronize()  # (the uploads above ran on the caller's stream; the kernels read them on the solver's)
@@ -213,7 +228,7 @@ class MPCController:
         Shapes as at construction: a controller built with static centres (K, pos_dim) keeps static ones.  Per-stage or per-particle
         centres are NOT moved along with the plan by `step`'s shift: stage j of the array is stage j of the next plan as it is, so a
         caller with moving obstacles sets them before every step."""
-        if self._cstr is None:
+        if self._cstr is None or self._custom_cstr:
             raise ValueError("MPCController.set_keepout: the controller was built without keepout=")
         cen, rad = self._cstr[1]
         if radius is not None and not bool((torch.as_tensor(radius) > 0).all()):
@@ -240,6 +255,21 @@ class MPCController:
         s._before()
         with torch.cuda.stream(s.stream):
             self._load(resident, cparams)
+        s._after()
+
+    def set_constraint_params(self, gparams):
+        """New parameters (M, pdim) of the custom constraint (`constraint=dict(cstr=, params=)`), copied into the resident array on the
+        solver's stream: the next step's linearisations read them."""
+        if not self._custom_cstr:
+            raise ValueError("MPCController.set_constraint_params: the controller was built without constraint=dict(cstr=, params=)")
+        resident, cc = self._cstr[1]
+        shape = tuple(gparams.shape) if hasattr(gparams, "shape") else np.shape(gparams)
+        if shape != tuple(resident.shape):
+            raise ValueError(f"{cc!r}: params must be (M, pdim) = {tuple(resident.shape)}, got {shape}")
+        s = self.solver
+        s._before()
+        with torch.cuda.stream(s.stream):
+            self._load(resident, gparams)
         s._after()
 
     # ---- one MPC step ----------------------------------------------------------------------------------------

@@ -29,6 +29,10 @@ particle stays outside 1 to 4 balls in the position sub-space `pos_idx` (centres
 and restates them as upper bounds on K auxiliary states (`DeviceSolver.keepout_augment`, a HIP kernel): the sub-problem runs at
 `xdim + K` states, the loop sees `xdim`.  The host loop's equivalent is `extra_cstrs_fns=make_keepout_extra_cstrs_fn(...)`.  Refused
 next to it: a stage cone (`soc=` / `extra_cstrs`), slew penalties, `smooth_cstr="squareplus"`, a sharded context, fp32 Jacobians.
+`builtin_cstr=dict(kind="custom", cstr=pmpc_amd.CustomConstraint, params=(M, pdim))` is the user's own state constraint g(x) <= 0, compiled
+at run time (csrc/cstr_jit.hip): `DeviceSolver.custom_cstr_rows` gives the rows about X_prev, `DeviceSolver.rows_augment` (a HIP kernel)
+restates them the same way; the same refusals hold, and a row whose value or gradient is not finite at an iterate is a `ValueError`.
+The host loop's equivalent is `extra_cstrs_fns=make_rows_extra_cstrs_fn(g_fn, jac_fn)`.
 
 Host-only features of the reference loop that need the sub-problem on the host (`extra_cstrs_fns`, filters, `solver_state`) are
 not offered here; `pmpc_amd.scp_mpc.scp_solve` (the default) has them.
@@ -41,8 +45,10 @@ import math
 import time
 from typing import Any, Callable, Dict, Optional
 
+import numpy as np
 import torch
 
+from .custom_constraint import check_cstr_dict, is_custom as is_custom_cstr
 from .custom_cost import is_custom
 from .custom_model import CustomModel
 from .device import DeviceSolver
@@ -92,6 +98,9 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
         raise ValueError(f"scp_solve(device=...) does not support {bad}; use the host loop (device=None)")
     if builtin_cstr is not None:
         _refuse_with_cstr(solver_settings, soc, slew_rate, u0_slew, solver)
+        if is_custom_cstr(builtin_cstr):  # dimensions and params that are not the problem's: before any device is touched
+            qs = tuple(Q.shape) if hasattr(Q, "shape") else np.shape(Q)
+            check_cstr_dict(builtin_cstr, qs[0] if len(qs) == 4 else 1, qs[-1])
     dev = torch.device(device)
     t_start = time.time()
     with_costs = lin_cost_fn is not None or builtin_cost is not None
@@ -119,6 +128,7 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
     if builtin_cstr is not None:
         _refuse_with_cstr(solver=s)
         cstr_handle = s.prepare_cstr(builtin_cstr, M, N, xdim, dev)
+        custom_cstr = cstr_handle[0].kind == 2
         static = keepout_buffers(p, cstr_handle[0].K, sets=1)  # (one set: nothing of the next iteration is enqueued behind this loop's solves)
         aug, Xs_aug = static["sets"][0], static["X_out"]
     it, max_res = 0, math.inf
@@ -161,7 +171,11 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
             # the keep-out rows about X_prev as bounds on K auxiliary states; the solve runs at xdim + K states.  prev_is_last_solution
             # stays off: X_prev~ holds zeros where the previous output holds the rows' values, so the flag's promise (X_prev is the
             # previous solve's output) does not hold for the augmented arrays
-            s.keepout_augment(cstr_handle, X_prev, f, fxa, fua, X_ref=X_ref_, out=aug)
+            if custom_cstr:
+                rows_a, rows_h = s.custom_cstr_rows(cstr_handle[0].id, X_prev, cstr_handle[1][0])
+                s.rows_augment(rows_a, rows_h, X_prev, f, fxa, fua, X_ref=X_ref_, out=aug)
+            else:
+                s.keepout_augment(cstr_handle, X_prev, f, fxa, fua, X_ref=X_ref_, out=aug)
             kw.update(f=aug["f"], fx=aug["fx"], fu=aug["fu"], X_prev=aug["X_prev"], X_ref=aug["X_ref"], Q=static["Qa"], x0=static["x0"], lx=static["lx"],
                       ux=aug["xu"], X_out=Xs_aug, prev_is_last_solution=False)
         if p.soc_kw:
@@ -183,6 +197,8 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
         if status != 0 or not bool(torch.isfinite(row).all()):  # solver failure (:391-394)
             if with_costs:  # ... which a Q / R block that is not positive definite causes (NaN references): say so
                 s.check_bad_pivots("lin_cost_fn / builtin_cost: Q or R")
+            if builtin_cstr is not None and custom_cstr:
+                s.check_bad_rows("builtin_cstr")
             if verbose:
                 print("Solver failed...")
             return None, None, None
@@ -202,6 +218,8 @@ def scp_solve_device(f_fx_fu_fn: Optional[Callable], Q, R, x0, X_ref=None, U_ref
         print(tp.make_footer())
     if with_costs:  # the shifts' device-side counter of refused blocks: read once, after the loop
         s.check_bad_pivots("lin_cost_fn / builtin_cost: Q or R")
+    if builtin_cstr is not None and custom_cstr:  # likewise the rows kernel's counter of rows it had to drop
+        s.check_bad_rows("builtin_cstr")
     X = torch.cat([p.x0[:, None, :], X_prev], 1)
     U = U_prev
     if single:
