@@ -400,6 +400,20 @@ int pmpc_as_sweep_resources(int sweep, int xdim, int udim, const int *variant, i
 int pmpc_as_sweep_launches(int sweep, unsigned long long *out, int n, int reset);
 void pmpc_as_sweep_knobs(int *out);
 
+/* The same count for the kernels that answer when the active-set rounds do not — the sweeps of the equality solve and of the
+ * interior-point iteration (kernels_fast.hip), the condensing kernels and the dense consensus solve —, for the tests that must know
+ * which of them a solve ran (tests/test_ipm_dims_gpu.py).  Host-side, every context and dims pair together, counted when enqueued:
+ *   kind 0 (k_bwd_fast, 16 codes):      factor + 2 * hxb + 4 * hub + 8 * deep   (factor 0: the vector-only sweep)
+ *   kind 1 (condensing, 2 codes):       0 k_cond_fast, 1 k_cond_fast_grouped
+ *   kind 2 (launch_cons_solve, 10 codes): variant + 5 * factor, variant 0 k_cons_solve, 1 k_cons_solve_blocked, 2 k_cons_solve_lds,
+ *                                       3 k_cons_solve_reg<12>, 4 k_cons_solve_reg<17> (the last two only factor)
+ * Kinds 0 and 1 are launches of the register-resident path only.  Kind 2 counts EVERY call of launch_cons_solve — the active-set
+ * rounds' and the generic kernels' solves too (both paths share the dense consensus solve) —, so a test that reads it runs nothing
+ * else between its reset and its reading.
+ * Writes the first min(n, codes) counts to out (may be NULL), zeroes the kind's counts if reset != 0, returns the number of codes
+ * (-1 for an unknown kind). */
+int pmpc_fast_launches(int kind, unsigned long long *out, int n, int reset);
+
 /* SCP residual of one iteration (pmpc/scp_mpc.py:397-403): *out (device, one double) = max over particles and stages of
  * ||X - X_prev||_2 and ||U - U_prev||_2 (inf if a trajectory holds a NaN); asynchronous on pmpc_stream(). */
 int pmpc_scp_residual_device(pmpc_ctx *ctx, size_t xdim, size_t udim, size_t N, size_t M, const double *X, const double *X_prev,

@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "pmpc_scp_residual_device", "pmpc_profile_read_partial", "pmpc_profile_read_all", "pmpc_scp_loop_device", "pmpc_linearize_device_f32",
     "pmpc_set_option", "pmpc_get_option", "pmpc_abi_struct_sizes", "pmpc_lcone_solve_host_ex", "pmpc_restart_stats",
     "pmpc_linearize_compact_device", "pmpc_expand_jac_device", "pmpc_jac_compact_doubles", "pmpc_jac_live_mask",
-    "pmpc_as_sweep_variant", "pmpc_as_sweep_launches", "pmpc_as_sweep_knobs", "pmpc_as_sweep_resources",
+    "pmpc_as_sweep_variant", "pmpc_as_sweep_launches", "pmpc_as_sweep_knobs", "pmpc_as_sweep_resources", "pmpc_fast_launches",
     "pmpc_ref_shift_device", "pmpc_ref_shift_bad_pivots", "pmpc_obstacle_cost_grad_device", "pmpc_obstacle_ref_shift_device",
     "pmpc_scp_loop_device_cost", "pmpc_abi_scp_cost_size",
     "pmpc_rollout_device", "pmpc_shift_plan_device",
@@ -177,6 +177,9 @@ def load():
         lib.pmpc_as_sweep_launches.restype = ctypes.c_int
         lib.pmpc_as_sweep_knobs.argtypes = [ctypes.POINTER(ctypes.c_int)]
         lib.pmpc_as_sweep_knobs.restype = None
+    if hasattr(lib, "pmpc_fast_launches"):  # (likewise)
+        lib.pmpc_fast_launches.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int, ctypes.c_int]
+        lib.pmpc_fast_launches.restype = ctypes.c_int
     if hasattr(lib, "pmpc_as_sweep_resources"):  # (likewise)
         lib.pmpc_as_sweep_resources.argtypes = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
         lib.pmpc_as_sweep_resources.restype = ctypes.c_int
@@ -352,6 +355,31 @@ def as_sweep_launches(sweep: str, reset: bool = False):
     n = lib.pmpc_as_sweep_launches(sw, None, 0, 0)
     out = (ctypes.c_ulonglong * n)()
     lib.pmpc_as_sweep_launches(sw, out, n, int(reset))
+    return [int(v) for v in out]
+
+
+FAST_LAUNCH_KINDS = {"sweep": 0, "cond": 1, "cons": 2}
+CONS_SOLVE_VARIANTS = ("plain", "blocked", "lds", "reg12", "reg17")
+
+
+def fast_sweep_code(factor, hxb, hub, deep) -> int:
+    """Where fast_launches("sweep") keeps the count of k_bwd_fast<.., FACTOR, HXB, HUB, DEEP> (include/pmpc_abi.h)."""
+    return int(bool(factor)) + 2 * int(bool(hxb)) + 4 * int(bool(hub)) + 8 * int(bool(deep))
+
+
+def cons_solve_code(variant: str, factor) -> int:
+    """Where fast_launches("cons") keeps the count of a dense consensus solve: variant of CONS_SOLVE_VARIANTS, factor or vector-only."""
+    return CONS_SOLVE_VARIANTS.index(variant) + 5 * int(bool(factor))
+
+
+def fast_launches(kind: str, reset: bool = False):
+    """Launch counts of this process's equality / interior-point kernels (pmpc_fast_launches): kind "sweep" indexed by fast_sweep_code,
+    "cond" by 0 k_cond_fast / 1 k_cond_fast_grouped, "cons" by cons_solve_code; reset: start counting afresh."""
+    lib = load()
+    kd = FAST_LAUNCH_KINDS[kind]
+    n = lib.pmpc_fast_launches(kd, None, 0, 0)
+    out = (ctypes.c_ulonglong * n)()
+    lib.pmpc_fast_launches(kd, out, n, int(reset))
     return [int(v) for v in out]
 
 

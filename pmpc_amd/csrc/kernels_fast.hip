@@ -33,6 +33,8 @@
 //
 // Reference semantics: same Newton system as kernels_generic.hip (PMPC.jl/src/lqp_utils.jl:2-393).
 #include "fast_common.h"
+#include <atomic>
+#include "../../include/pmpc_abi.h"
 
 namespace {
 
@@ -798,7 +800,7 @@ void launch_bwd_t(const LQArgs &a, bool factor, hipStream_t s) {
   const bool deep = a.M <= 3 * 1024;
   const dim3 grd(a.M), blk(64);
 #define PMPC_BWD(F, XB, UB, DP) hipLaunchKernelGGL((k_bwd_fast<XD, UD, F, XB, UB, DP>), grd, blk, 0, s, a)
-#define PMPC_BWD2(F, XB, UB) do { if (deep) PMPC_BWD(F, XB, UB, true); else PMPC_BWD(F, XB, UB, false); } while (0)
+#define PMPC_BWD2(F, XB, UB) do { if (deep) PMPC_BWD(F, XB, UB, true); else PMPC_BWD(F, XB, UB, false); count_fast_launch(0, (F) + 2 * (XB) + 4 * (UB) + 8 * deep); } while (0)
   if (factor) {
     if (xb && ub) PMPC_BWD2(true, true, true);
     else if (xb) PMPC_BWD2(true, true, false);
@@ -818,6 +820,7 @@ void launch_cond_t(const LQArgs &a, hipStream_t s) {
   const int ntiles = (a.Nc * UD + 15) / 16;
   if (a.Hc_grp) hipLaunchKernelGGL((k_cond_fast_grouped<XD, UD>), dim3((a.M + COND_GRP - 1) / COND_GRP, (ntiles + COND_TPW - 1) / COND_TPW), dim3(64 * COND_GRP), 0, s, a);
   else hipLaunchKernelGGL((k_cond_fast<XD, UD>), dim3(a.M, (ntiles + COND_TPW - 1) / COND_TPW), dim3(64), 0, s, a);
+  count_fast_launch(1, a.Hc_grp ? 1 : 0);
 }
 template <int XD, int UD>
 void launch_fwd_t(const LQArgs &a, hipStream_t s) {
@@ -829,6 +832,24 @@ void launch_rollout_t(const LQArgs &a, const double *U, double *X, hipStream_t s
 }
 
 }  // namespace
+
+// launches per kernel of the equality / interior-point path since the process started (or the last reset), all pairs and contexts
+// together: pmpc_fast_launches (include/pmpc_abi.h states the codes)
+namespace {
+constexpr int FAST_LAUNCH_CODES[3] = {16, 2, 10};
+std::atomic<unsigned long long> fast_launches[3][16];
+}  // namespace
+void count_fast_launch(int kind, int code) { fast_launches[kind][code].fetch_add(1, std::memory_order_relaxed); }
+int pmpc_fast_launches(int kind, unsigned long long *out, int n, int reset) {
+  if (kind < 0 || kind > 2) return -1;
+  const int codes = FAST_LAUNCH_CODES[kind];
+  for (int c = 0; c < codes; c++) {
+    std::atomic<unsigned long long> &t = fast_launches[kind][c];
+    const unsigned long long v = reset ? t.exchange(0, std::memory_order_relaxed) : t.load(std::memory_order_relaxed);
+    if (out && c < n) out[c] = v;
+  }
+  return codes;
+}
 
 bool lq_fast_supported(const LQArgs &a) {
   if (a.w != 0 || a.any_slew || !a.sym_cost) return false;

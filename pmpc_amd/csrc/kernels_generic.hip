@@ -639,9 +639,10 @@ __global__ void __launch_bounds__(PMPC_CONS_BLOCKED_THREADS) k_cons_solve_blocke
 // order by gridDim.x slices (stage 1: outH/outg hold one partial per slice) and a final single block
 // (stage 2, gridDim.x == 1, solve_now) sums the slices and solves the dense system.  with_H = 0: gradient
 // only, stored factor.
-// LDS-resident variant of k_cons_solve_blocked for 16 < nc <= 88 (the whole factor in LDS, 1024 threads, no global
-// read-modify-write between panels) with the inverses of the 16 x 16 diagonal blocks kept next to the factor: the panel solve
-// of the factorisation and both substitutions become small matrix products instead of 16-step dependent chains.
+// LDS-resident variant of k_cons_solve_blocked for 16 < nc <= 72 (what launch_cons_solve fits into 64 KB; the whole factor in
+// LDS, 1024 threads, no global read-modify-write between panels) with the inverses of the 16 x 16 diagonal blocks kept next to
+// the factor: the panel solve of the factorisation and both substitutions become small matrix products instead of 16-step
+// dependent chains.
 // Lc: nc x nc factor (column-major lower) followed by ceil(nc / 16) inverse blocks of 16 x 17 doubles (for the vector-only
 // solves that follow a factorisation).  Same arithmetic order for every caller: all ranks get the same bits.
 __global__ void __launch_bounds__(1024) k_cons_solve_lds(const double *Hc, double *Lc, const double *gc, double *duc, int nc, int factor,
@@ -1271,18 +1272,22 @@ void launch_cons_solve(double *Hc, double *Lc, const double *gc, double *duc, in
     const int nb = (nc + 1 + 15) / 16, slots = (nb * (nb + 1) / 2 + CONS_REG_NW - 1) / CONS_REG_NW;
     if (slots <= 12) hipLaunchKernelGGL(k_cons_solve_reg<12>, dim3(1), dim3(CONS_REG_NTH), CONS_REG_LDS, s, (const double *)Hc, Lc, gc, duc, nc, fail);
     else hipLaunchKernelGGL(k_cons_solve_reg<17>, dim3(1), dim3(CONS_REG_NTH), CONS_REG_LDS, s, (const double *)Hc, Lc, gc, duc, nc, fail);
+    count_fast_launch(2, (slots <= 12 ? 3 : 4) + 5);
     return;
   }
-  // LDS-resident factor (+ inverse diagonal blocks + a 16-column scratch panel): up to nc = 80 inside 64 KB
+  // LDS-resident factor (+ inverse diagonal blocks + a 16-column scratch panel): up to nc = 72 inside 64 KB
   const int npan = (nc + 15) / 16;
   const size_t lds_full = ((size_t)nc * nc + nc + 16 * 17 + (size_t)npan * 272 + (size_t)16 * nc) * sizeof(double);
   static const bool lds_on = !(getenv("PMPC_CONS_LDS") && atoi(getenv("PMPC_CONS_LDS")) == 0);
   if (lds_on && nc > 16 && lds_full <= 64 * 1024) {
     hipLaunchKernelGGL(k_cons_solve_lds, dim3(1), dim3(1024), lds_full, s, (const double *)Hc, Lc, gc, duc, nc, factor ? 1 : 0, fail);
+    count_fast_launch(2, 2 + 5 * factor);
     return;
   }
   const size_t lds = ((size_t)17 * nc + 16 * 17) * sizeof(double);
-  if (nc > 16 && lds <= 64 * 1024)
+  const bool blocked = nc > 16 && lds <= 64 * 1024;
+  count_fast_launch(2, (blocked ? 1 : 0) + 5 * factor);
+  if (blocked)
     hipLaunchKernelGGL(k_cons_solve_blocked, dim3(1), dim3(PMPC_CONS_BLOCKED_THREADS), lds, s, (const double *)Hc, Lc, gc, duc, nc, factor ? 1 : 0, fail);
   else
     hipLaunchKernelGGL(k_cons_solve, dim3(1), dim3(256), nc * sizeof(double), s, (const double *)Hc, Lc, gc, duc, nc,

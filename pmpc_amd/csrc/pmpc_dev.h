@@ -246,6 +246,8 @@ int cond_fast_groups(int M);  // slabs of LQArgs::Hc_grp
 void launch_cond_fast(const LQArgs &a, hipStream_t s);  // off-diagonal blocks of the condensed consensus Hessian (Nc > 1)
 void launch_rollout_fast(const LQArgs &a, const double *U, double *X, hipStream_t s);
 void launch_grad_prep(const LQArgs &a, hipStream_t s);
+// one more launch of a kernel of the equality / interior-point path: kind and code of pmpc_fast_launches (include/pmpc_abi.h)
+void count_fast_launch(int kind, int code);
 // generic-path active-set rounds: counters[3] <- *fail (fail != null) and / or publication of counters[0..3] (mirror_cnt != null)
 void launch_as_publish(int *counters, const int *fail, int *mirror_cnt, unsigned long long *mirror_seq, unsigned long long seq, hipStream_t s);
 // J[i] = 1/2 z_i' P_i z_i + q_i' z_i + r_i of PMPC.jl/src/qp_utils.jl:60-162 at (X, U) (unweighted), any dims / slew
