@@ -8,7 +8,6 @@
 
 bool custom_cost_known(const pmpc_ctx *c, int id);                              // a cost id loaded on this context
 bool custom_cost_dims(int id, int *xdim, int *udim, int *cdim, int *uses_u);    // false: no such loaded cost (null outputs are skipped)
-void custom_costs_unload_all(pmpc_ctx *c);                                      // pmpc_destroy
 // cx (M, N, x), cu (M, N, u; not touched by a cost compiled with uses_u = 0), val (M, N) or null: one launch of pmpc_jit_cost_grad
 void custom_launch_cost_grad(int id, int N, int M, const double *X_prev, const double *U_prev, const double *cparams, double *cx, double *cu,
                              double *val, hipStream_t s);

@@ -8,7 +8,6 @@
 
 bool custom_cstr_known(const pmpc_ctx *c, int id);               // a constraint id loaded on this context
 bool custom_cstr_dims(int id, int *xdim, int *kdim, int *pdim);  // false: no such loaded constraint (null outputs are skipped)
-void custom_cstrs_unload_all(pmpc_ctx *c);                       // pmpc_destroy
 // a (M, N, K, x), h (M, N, K), g (M, N, K) or null: one launch of pmpc_jit_cstr_rows; *bad counts the rows it refused
 void custom_launch_cstr_rows(int id, int N, int M, const double *X_prev, const double *gparams, double *a, double *h, double *g, unsigned *bad,
                              hipStream_t s);

@@ -4,25 +4,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <string>
-
 #include "../../include/pmpc_abi.h"
 
 inline bool model_custom(int model) { return model >= PMPC_MODEL_CUSTOM0; }
 bool model_known(const pmpc_ctx *c, int model);           // a built-in id, or a custom id loaded on this context
 bool custom_model_dims(int model, int *xdim, int *udim);  // false: no such loaded model
-void custom_models_unload_all(pmpc_ctx *c);               // pmpc_destroy
 // the arguments of launch_linearize / launch_rollout / launch_shift_plan (pmpc_dev.h); fx / fu are always doubles
 void custom_launch_linearize(int model, int N, int M, const double *x0, const double *X_prev, const double *U_prev, const double *params,
                              double *f, double *fx, double *fu, hipStream_t s);
 void custom_launch_rollout(int model, int N, int M, const double *x0, const double *U, const double *params, double *X, hipStream_t s);
 void custom_launch_shift_plan(int model, int N, int M, int sh, const double *X, const double *U, const double *params, const double *U_tail,
                               double *Xn, double *Un, double *um1n, hipStream_t s);
-
-// The runtime compile that models and costs (cost_jit.hip) share: `program` with `nheaders` in-memory headers for the target id `arch`
-// (a feature suffix is dropped).  0: *code (malloc'd) holds *bytes; 1 bad arch; 2 no runtime compiler; 3 compile error; the
-// compiler's text goes to log.  `who` / `what`: the entry point and its subject, for the messages.
-int jit_compile(const char *who, const char *what, const std::string &program, const char *program_name, int nheaders, const char *const *headers,
-                const char *const *names, const char *arch, void **code, size_t *bytes, char *log, size_t log_cap);
-void jit_write_log(char *log, size_t cap, const std::string &text);
-const char *jit_dual_header();  // the text of model_dual.h

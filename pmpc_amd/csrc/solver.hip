@@ -15,6 +15,7 @@
 #include "model_jit.h"
 #include "cost_jit.h"
 #include "cstr_jit.h"
+#include "jit_module.h"
 
 static const struct { const char *key, *env; double dflt; } kPmpcOptions[OPT_COUNT] = {
     {"as_warm", "PMPC_AS_WARM", 1},                // warm start of the active-set rounds from the previous solve's set
@@ -280,9 +281,7 @@ void pmpc_destroy(pmpc_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  custom_models_unload_all(c);  // runtime-compiled models loaded on this context (model_jit.hip)
-  custom_costs_unload_all(c);   // ... and stage costs (cost_jit.hip)
-  custom_cstrs_unload_all(c);   // ... and state constraints (cstr_jit.hip)
+  jit_unload_all(c);  // the runtime-compiled models, stage costs and state constraints loaded on this context (jit_module.hip)
   comm_release(c);
   Workspace &w = c->ws;
   DevBuf *all[] = {&w.X, &w.U, &w.dX, &w.dU, &w.dX2, &w.dU2, &w.xm, &w.xd, &w.um, &w.ud, &w.K, &w.Hinv, &w.kff, &w.gc_part, &w.Hc_part, &w.Hc_w, &w.gc_w, &w.cons_w, &w.epi_lam, &w.epi_out, &w.epi_gath, &w.es_Dx, &w.es_wx, &w.es_Du, &w.es_wu, &w.es_xm, &w.es_xd, &w.es_um, &w.es_ud, &w.es_kff2, &w.es_kff3, &w.es_gc2, &w.es_dots, &w.es_coef, &w.es_out2, &w.es_Xt, &w.es_Ut, &w.es_U, &w.es_zero, &w.scratch,

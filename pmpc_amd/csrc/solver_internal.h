@@ -10,6 +10,8 @@
 //   solver_cone_smooth.hip  the cone objective with smoothed boxes: the full-space Newton iteration (lcone_smooth_body)
 //   cone_common.h    what those bodies set up alike: sweep arguments, zero buffers, consensus horizon, triangle mirror, memory keys
 //   solver_host.hip  the host-pointer drop-in entry points (c_lqp_solve, c_lcone_solve and their extensions)
+//   jit_module.hip   runtime-compiled code: the hiprtc compile and the tables of loaded code objects, written once for the three kinds;
+//                    model_jit.hip / cost_jit.hip / cstr_jit.hip hold each kind's limits, define list, launchers and entry points
 #pragma once
 #include <dlfcn.h>
 #include <rccl/rccl.h>

@@ -19,22 +19,20 @@ must hold symmetric positive definite blocks stored as float64.  Compiling needs
 """
 from __future__ import annotations
 
-import ctypes
-from typing import Dict, Optional
+from typing import Optional
 
-from . import _lib
+from .custom_jit import CustomCode, check_custom_dict, is_custom  # noqa: F401 (is_custom: imported from here by others)
 
 MAX_DIM, MAX_PDIM = 16, 64  # states and controls: the solver's limits; parameters are read from global memory
 
 
-class CustomCost:
+class CustomCost(CustomCode):
     def __init__(self, cost_source: str, xdim: int, udim: int, pdim: int, uses_u: bool = True, name: Optional[str] = None):
         self.cost_source, self.name = str(cost_source), name
         self.xdim, self.udim, self.pdim, self.uses_u = int(xdim), int(udim), int(pdim), bool(uses_u)
         for what, d, hi in (("xdim", self.xdim, MAX_DIM), ("udim", self.udim, MAX_DIM), ("pdim", self.pdim, MAX_PDIM)):
             if not 1 <= d <= hi:
                 raise ValueError(f"CustomCost: {what} = {d} is outside 1 .. {hi}")
-        self._code: Dict[str, bytes] = {}
 
     def __repr__(self):
         return f"CustomCost({self.name or 'unnamed'}, xdim={self.xdim}, udim={self.udim}, pdim={self.pdim}, uses_u={self.uses_u})"
@@ -42,49 +40,16 @@ class CustomCost:
     def compile(self, arch: str = "gfx950") -> bytes:
         """The code object for `arch` (a target id; what follows a ':' is dropped), compiled once per object and architecture.
         A compile error is a ValueError that carries the compiler's log; a missing runtime compiler a RuntimeError."""
-        arch = str(arch).split(":")[0]
-        if arch not in self._code:
-            lib = _lib.load()
-            if not hasattr(lib, "pmpc_cost_compile"):
-                raise RuntimeError(f"{_lib.LIB_PATH} has no pmpc_cost_compile: it predates custom costs, rebuild it (make -C pmpc_amd/csrc)")
-            code, n = ctypes.c_void_p(), ctypes.c_size_t(0)
-            log = ctypes.create_string_buffer(1 << 16)
-            rc = lib.pmpc_cost_compile(self.cost_source.encode(), self.xdim, self.udim, self.pdim, int(self.uses_u), arch.encode(), ctypes.byref(code),
-                                       ctypes.byref(n), log, len(log))
-            text = log.value.decode(errors="replace")
-            if rc == 2:
-                raise RuntimeError(f"CustomCost.compile: {text or 'the runtime compiler is not available'}")
-            if rc != 0:
-                raise ValueError(f"{self!r} does not compile for {arch}:\n{text}")
-            try:
-                self._code[arch] = ctypes.string_at(code, n.value)
-            finally:
-                lib.pmpc_model_free_code(code)
-        return self._code[arch]
+        return self._compile("pmpc_cost_compile", "custom costs", self.cost_source, (self.xdim, self.udim, self.pdim, int(self.uses_u)), arch)
 
     def check_problem(self, M: int, xdim: int, udim: int, params) -> None:
         """Refuse a problem whose Q / R dimensions or `params` (M, pdim) are not this cost's (host-side: no device is touched)."""
-        import numpy as np
-
         if (int(xdim), int(udim)) != (self.xdim, self.udim):
             raise ValueError(f"{self!r}: the problem has Q (.., {xdim}, {xdim}) and R (.., {udim}, {udim}), not the cost's dimensions")
-        shape = tuple(params.shape) if hasattr(params, "shape") else np.shape(params)
-        if shape != (int(M), self.pdim):
-            raise ValueError(f"{self!r}: params must be (M, pdim) = ({M}, {self.pdim}), got {shape}")
-
-
-def is_custom(cost) -> bool:
-    return isinstance(cost, dict) and cost.get("kind") == "custom"
+        self._check_params(M, params)
 
 
 def check_cost_dict(cost, M: int, xdim: int, udim: int) -> None:
     """The host-side refusals of dict(kind="custom", cost=, params=): no CustomCost, dimensions that are not the problem's, params that
     are not (M, pdim).  Any other cost passes (the built-in ones have checks of their own)."""
-    if not is_custom(cost):
-        return
-    cc = cost.get("cost")
-    if not isinstance(cc, CustomCost):
-        raise ValueError(f'dict(kind="custom") needs cost=, a pmpc_amd.CustomCost (got {type(cc).__name__})')
-    if cost.get("params") is None:
-        raise ValueError(f'dict(kind="custom") needs params=, the cost parameters (M, pdim) = ({M}, {cc.pdim})')
-    cc.check_problem(M, xdim, udim, cost["params"])
+    check_custom_dict(cost, "cost", CustomCost, "cost", M, xdim, udim)

@@ -19,22 +19,20 @@ the id-taking methods `linearize`, `rollout`, `shift_plan`, `scp_loop`.  Compili
 """
 from __future__ import annotations
 
-import ctypes
-from typing import Dict, Optional
+from typing import Optional
 
-from . import _lib
+from .custom_jit import CustomCode
 
 MAX_DIM = 16  # states, controls, parameters: the solver's own limits
 
 
-class CustomModel:
+class CustomModel(CustomCode):
     def __init__(self, step_source: str, xdim: int, udim: int, pdim: int, name: Optional[str] = None):
         self.step_source, self.name = str(step_source), name
         self.xdim, self.udim, self.pdim = int(xdim), int(udim), int(pdim)
         for what, d in (("xdim", self.xdim), ("udim", self.udim), ("pdim", self.pdim)):
             if not 1 <= d <= MAX_DIM:
                 raise ValueError(f"CustomModel: {what} = {d} is outside 1 .. {MAX_DIM}")
-        self._code: Dict[str, bytes] = {}
 
     def __repr__(self):
         return f"CustomModel({self.name or 'unnamed'}, xdim={self.xdim}, udim={self.udim}, pdim={self.pdim})"
@@ -42,23 +40,7 @@ class CustomModel:
     def compile(self, arch: str = "gfx950") -> bytes:
         """The code object for `arch` (a target id; what follows a ':' is dropped), compiled once per object and architecture.
         A compile error is a ValueError that carries the compiler's log."""
-        arch = str(arch).split(":")[0]
-        if arch not in self._code:
-            lib = _lib.load()
-            code, n = ctypes.c_void_p(), ctypes.c_size_t(0)
-            log = ctypes.create_string_buffer(1 << 16)
-            rc = lib.pmpc_model_compile(self.step_source.encode(), self.xdim, self.udim, self.pdim, arch.encode(), ctypes.byref(code), ctypes.byref(n),
-                                        log, len(log))
-            text = log.value.decode(errors="replace")
-            if rc == 2:
-                raise RuntimeError(f"CustomModel.compile: {text or 'the runtime compiler is not available'}")
-            if rc != 0:
-                raise ValueError(f"{self!r} does not compile for {arch}:\n{text}")
-            try:
-                self._code[arch] = ctypes.string_at(code, n.value)
-            finally:
-                lib.pmpc_model_free_code(code)
-        return self._code[arch]
+        return self._compile("pmpc_model_compile", "custom models", self.step_source, (self.xdim, self.udim, self.pdim), arch)
 
     def check_problem(self, M: int, xdim: int, udim: int, params) -> None:
         """Refuse a problem whose Q / R dimensions or `params` (M, pdim) are not this model's (host-side: no device is touched)."""

@@ -15,6 +15,14 @@ from . import _lib
 
 MODEL_UNICYCLE, MODEL_QUADROTOR, MODEL_BICYCLE = 0, 1, 2
 
+# The kinds of runtime-compiled code a solver loads, by the word the messages use: the solver's dict of loaded objects, the prefix of the
+# library's _load / _unload entry points, the int arguments of _load taken from the object, the first id.
+_JIT_KINDS = {
+    "model": ("_custom", "pmpc_model", lambda o: (o.xdim, o.udim, o.pdim), _lib.MODEL_CUSTOM0),
+    "cost": ("_costs", "pmpc_cost", lambda o: (o.xdim, o.udim, o.pdim, int(o.uses_u)), _lib.COST_CUSTOM0),
+    "constraint": ("_cstrs", "pmpc_cstr", lambda o: (o.xdim, o.kdim, o.pdim), _lib.CSTR_CUSTOM0),
+}
+
 
 def _p(t: Optional[torch.Tensor], dtype=torch.float64):
     if t is None:
@@ -53,27 +61,37 @@ class DeviceSolver:
         self._costs: Dict[int, object] = {}  # cost id -> the CustomCost loaded under it (load_cost); a table apart from the models'
         self._cstrs: Dict[int, object] = {}  # constraint id -> the CustomConstraint loaded under it (load_cstr); likewise
 
+    # ---- runtime-compiled code: one load and one unload for the three kinds (_JIT_KINDS) ---------------
+    def _load_custom(self, kind, obj) -> int:
+        attr, prefix, ints, first_id = _JIT_KINDS[kind]
+        self._need(prefix + "_load")
+        loaded = getattr(self, attr)
+        for i, o in loaded.items():
+            if o is obj:
+                return i
+        arch = torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0]  # the target id alone, never a feature suffix
+        code = obj.compile(arch)
+        i = getattr(self.lib, prefix + "_load")(self.h, code, len(code), *ints(obj))
+        if i < first_id:
+            raise RuntimeError(f"{prefix}_load failed ({i}) for {obj!r}")
+        loaded[i] = obj
+        return i
+
+    def _unload_custom(self, kind, i) -> None:
+        attr, prefix, _, _ = _JIT_KINDS[kind]
+        getattr(self, attr).pop(int(i), None)
+        if getattr(self.lib, prefix + "_unload")(self.h, int(i)) != 0:
+            raise ValueError(f"{kind} {i} is not a custom {kind} loaded on this solver")
+
     # ---- runtime-compiled dynamics models (pmpc_amd/custom_model.py) -----------------------------------
     def load_model(self, cm) -> int:
         """The model id (>= 1000) of a `pmpc_amd.CustomModel` on this solver: compiled for the device's architecture and loaded on
         first use, the same id from then on.  `linearize`, `rollout`, `shift_plan` and `scp_loop` take it as they take 0 - 2; it is
         known to this solver only and goes with `unload_model` or `close`."""
-        self._need("pmpc_model_load")
-        for mid, loaded in self._custom.items():
-            if loaded is cm:
-                return mid
-        arch = torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0]  # the target id alone, never a feature suffix
-        code = cm.compile(arch)
-        mid = self.lib.pmpc_model_load(self.h, code, len(code), cm.xdim, cm.udim, cm.pdim)
-        if mid < _lib.MODEL_CUSTOM0:
-            raise RuntimeError(f"pmpc_model_load failed ({mid}) for {cm!r}")
-        self._custom[mid] = cm
-        return mid
+        return self._load_custom("model", cm)
 
     def unload_model(self, model: int) -> None:
-        self._custom.pop(int(model), None)
-        if self.lib.pmpc_model_unload(self.h, int(model)) != 0:
-            raise ValueError(f"model {model} is not a custom model loaded on this solver")
+        self._unload_custom("model", model)
 
     def _check_custom(self, model, M, x=None, u=None, params=None):
         """A loaded custom model reads x, u and pdim values per unit whatever the tensors hold: shapes that are not its own are
@@ -91,22 +109,10 @@ class DeviceSolver:
         """The cost id (>= 1000, in a table of its own: it means a cost only where a cost is asked for) of a `pmpc_amd.CustomCost` on
         this solver: compiled for the device's architecture and loaded on first use, the same id from then on.  It is known to this
         solver only and goes with `unload_cost` or `close`."""
-        self._need("pmpc_cost_load")
-        for cid, loaded in self._costs.items():
-            if loaded is cc:
-                return cid
-        arch = torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0]  # the target id alone, never a feature suffix
-        code = cc.compile(arch)
-        cid = self.lib.pmpc_cost_load(self.h, code, len(code), cc.xdim, cc.udim, cc.pdim, int(cc.uses_u))
-        if cid < _lib.COST_CUSTOM0:
-            raise RuntimeError(f"pmpc_cost_load failed ({cid}) for {cc!r}")
-        self._costs[cid] = cc
-        return cid
+        return self._load_custom("cost", cc)
 
     def unload_cost(self, cost: int) -> None:
-        self._costs.pop(int(cost), None)
-        if self.lib.pmpc_cost_unload(self.h, int(cost)) != 0:
-            raise ValueError(f"cost {cost} is not a custom cost loaded on this solver")
+        self._unload_custom("cost", cost)
 
     def custom_cost_grad(self, cost, X_prev, U_prev, cparams, value=False, cx=None, cu=None, wait_current_stream=True):
         """(cx (M, N, x), cu (M, N, u)) — with `value` also val (M, N), the stage values — of a custom cost at (X_prev, U_prev) with the
@@ -141,22 +147,10 @@ class DeviceSolver:
         """The constraint id (>= 1000, in a table of its own) of a `pmpc_amd.CustomConstraint` on this solver: compiled for the device's
         architecture and loaded on first use, the same id from then on.  It is known to this solver only and goes with `unload_cstr` or
         `close`."""
-        self._need("pmpc_cstr_load")
-        for gid, loaded in self._cstrs.items():
-            if loaded is cc:
-                return gid
-        arch = torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0]  # the target id alone, never a feature suffix
-        code = cc.compile(arch)
-        gid = self.lib.pmpc_cstr_load(self.h, code, len(code), cc.xdim, cc.kdim, cc.pdim)
-        if gid < _lib.CSTR_CUSTOM0:
-            raise RuntimeError(f"pmpc_cstr_load failed ({gid}) for {cc!r}")
-        self._cstrs[gid] = cc
-        return gid
+        return self._load_custom("constraint", cc)
 
     def unload_cstr(self, cstr: int) -> None:
-        self._cstrs.pop(int(cstr), None)
-        if self.lib.pmpc_cstr_unload(self.h, int(cstr)) != 0:
-            raise ValueError(f"constraint {cstr} is not a custom constraint loaded on this solver")
+        self._unload_custom("constraint", cstr)
 
     def check_bad_rows(self, what):
         """Raise ValueError if the rows kernel of a custom constraint since the last check met a row whose value or gradient is not finite
